@@ -2,6 +2,8 @@
 """bench.py -- env-steps/s of the batched Kuka env on N MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: spawns one rank per GPU itself
+    python bench.py --gpus N --steps K --warmup W --full   # + full_episodes, host_api and (one GPU) cpu_baseline
+    python bench.py ... --dump-outputs DIR                 # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # or is launched per rank
 
 One "step" = one batched env.step() over 4096 envs per GPU (BASELINE.json configs[1]: task='reach', 4096 vectorised
@@ -13,8 +15,15 @@ episode just ended (pmg_reset_done_device: the device finds them by their elapse
 the timed region.  Any window of K steps therefore sees every episode phase in the same
 proportion, and `value` no longer depends on where in an episode a short window falls (`--lockstep` restores the old
 all-envs-in-phase loop).  W untimed warm-up steps, then EXACTLY K timed steps between barrier + stream sync; the slowest
-rank's time counts; rank 0 prints ONE JSON line.  Secondary fields, never `value`: `full_episodes` (the same loop over
-two whole episodes) and `host_api` (numpy in / numpy out through env.step(), PCIe inclusive).
+rank's time counts; rank 0 prints ONE JSON line.  A plain run does only that: set up, pre-roll, warm up, time the K steps,
+write the outputs (--dump-outputs) and print the line.  Secondary fields, never `value`, only with --full: `full_episodes`
+(the same loop over two whole episodes), `host_api` (numpy in / numpy out through env.step(), PCIe inclusive) and, on one
+GPU, `cpu_baseline` (the CPU oracle on the host cores, ~12 s).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path left for its caller in the last step (the
+packed rows of pmg_step_device + pmg_reset_done_device, split as pmg_read_outputs splits them) as DIR/<name>.npy, float32.
+The inputs depend on the arguments alone (seeded actions, seed_base 0), so two builds can be compared output for output.
+Above DUMP_MAX_BYTES, a fixed seeded sample of envs is written, with its env indices in env_index.npy.
 
 The env is the C-ABI HIP library (ctypes).  No PyTorch anywhere: the ranks rendezvous over stdlib TCP
 (pybullet_multigoal_gym_amd.distributed.Rendezvous) for the 128-byte RCCL id, the barriers and the max over ranks.
@@ -42,6 +51,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
 # MI355X_MICROARCH.md "Wave scheduling": 256 CUs x 4 SIMD-32; a wave64 VALU instruction issues over 2 cycles
 VALU_PEAK_INSTS = 1024 * 2.4e9 / 2          # 1.2288e12 wave-instructions / s
 FP32_PEAK_TFLOPS = 157.3                    # 256 CU x 4 SIMD x 32 lanes x 2 flop x 2.4 GHz (vector fp32, = the fp32 MFMA rate)
+DUMP_MAX_BYTES = 64 << 20                   # --dump-outputs: at most this much in all
 
 
 def _committed(pattern):
@@ -143,6 +153,24 @@ def cpu_baseline(task, budget_s=12.0):
                       'reference may be read off it' % (n, steps, task, cores)}
 
 
+def dump_outputs(h, out_dir):
+    """The outputs of the last batched step as a caller of the device path reads them (pmg_read_outputs), one float32
+    .npy per array; envs sampled with a fixed seed when all of them would exceed DUMP_MAX_BYTES."""
+    o, p, ag, dg, r, ok, dn = h.read_outputs()
+    arrays = {'observation': o, 'policy_state': p, 'achieved_goal': ag, 'desired_goal': dg, 'reward': r,
+              'goal_achieved': ok, 'done': dn}
+    n = h.N
+    row_bytes = 4 * sum(a[0].size for a in arrays.values())
+    if n * row_bytes > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)    # + 8 B per sampled env (its index, float64); 4 KB of .npy headers
+        idx = np.sort(np.random.RandomState(0).choice(n, m, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays['env_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, np.float64 if k == 'env_index' else np.float32))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: spawn one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE in the env,
     a free TCP port for the rendezvous) and pass rank 0's line through."""
@@ -170,8 +198,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--task', default='reach')
     ap.add_argument('--envs-per-gpu', type=int, default=4096)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the secondary full_episodes / host_api measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also the secondary measurements: full_episodes, host_api and (one GPU) cpu_baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the secondary full_episodes / host_api measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (rank 0's envs) as DIR/<name>.npy, float32")
     ap.add_argument('--episode-steps', type=int, default=50)
     ap.add_argument('--dense-reward', action='store_true', help='binary_reward=False (BASELINE.json configs[3] runs both)')
     ap.add_argument('--lib', default=None, help='alternative libpmg_hip.so build (kernel A/B experiments)')
@@ -239,7 +271,7 @@ def main():
             collective = 'FALLBACK: RCCL init failed, host all-gather of packed obs (PCIe + TCP inclusive)'
             host_gather = True
     # synthetic random policy: a table of batches of U(-1,1) float32 actions, resident in HBM
-    E = 0 if args.no_extras else 2 * T                     # extra whole episodes for the secondary measurement
+    E = 2 * T if args.full and not args.no_extras else 0  # extra whole episodes for the secondary measurement
     stagger = not args.lockstep
     P = T if stagger else 0                                # untimed pre-roll: one episode, brings env i to phase i mod T
     table = np.random.RandomState(12345 + rank).uniform(-1, 1, (P + K + W + E, N, A)).astype(np.float32)
@@ -318,6 +350,8 @@ def main():
     el = timed_keep(P + W, K)
     hg_ms = host_gather_s[0] / max(1, host_gather_s[1]) * 1e3
     kmin, kernel_ms, kmax, launches = h.timing_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(h, args.dump_outputs)                 # before the --full extras step the envs any further
     per_rank = None
     if multi:
         # diagnosability of the N > 1 run: every rank's own wall clock, step-kernel average and all-gather events
@@ -422,7 +456,7 @@ def main():
             out['full_episodes'] = full
         if host is not None:
             out['host_api'] = host
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.task)
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if os.environ.get('PMG_ASSERT_NO_TORCH') and rank == 0:   # test hook: the ranks run without PyTorch

@@ -254,3 +254,42 @@ def test_no_dpp_hazard_in_the_shipped_binary(built):
     import check_dpp_hazards as H
     ndpp, bad_exec, bad_src, valu_exec = H.check_binary(H.disassemble(os.path.join(ROOT, 'pybullet_multigoal_gym_amd', 'csrc', 'libpmg_hip.so')))
     assert ndpp > 10000 and bad_exec == 0 and bad_src == 0, (ndpp, bad_exec, bad_src, valu_exec)
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(built, tmp_path):
+    """bench.py on the emulator build: a plain run prints the headline line without the secondary measurements, and
+    --dump-outputs writes the last timed step's outputs as float32 .npy, the same in two runs with the same arguments;
+    --full brings full_episodes / host_api back."""
+    import json
+    import subprocess
+    import sys
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--envs-per-gpu', '4',
+            '--episode-steps', '2', '--lib', os.path.join(ROOT, 'tests', 'emu', 'libpmg_emu.so')]
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None)
+
+    def run(*extra):
+        out = subprocess.run(base + list(extra), cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    dumps = [tmp_path / 'a', tmp_path / 'b']
+    for d in dumps:
+        line = run('--dump-outputs', str(d))
+        assert line['steps'] == 3 and line['roofline']['launches'] == 3
+        assert abs(line['value'] - 4 * 3 / (line['ms_per_step'] * 3e-3)) < 1e-6 * line['value']
+        for k in ('metric', 'unit', 'higher_is_better', 'dtype'):
+            assert k in line, k
+        for k in ('full_episodes', 'host_api', 'cpu_baseline'):
+            assert k not in line, k
+    names = {'observation': 3, 'policy_state': 3, 'achieved_goal': 3, 'desired_goal': 3, 'reward': 1, 'goal_achieved': 1, 'done': 1}
+    assert sorted(p.name for p in dumps[0].iterdir()) == sorted(n + '.npy' for n in names)
+    for n, width in names.items():
+        a, b = np.load(dumps[0] / (n + '.npy')), np.load(dumps[1] / (n + '.npy'))
+        assert a.dtype == np.float32 and a.shape[0] == 4 and (a.ndim == 1) == (width == 1), n
+        assert np.array_equal(a, b), n
+    assert np.isin(np.load(dumps[0] / 'done.npy'), (0.0, 1.0)).all()
+    line = run('--full', '--no-cpu-baseline')
+    assert line['full_episodes']['steps'] == 4 and line['host_api']['steps'] == 2 and 'cpu_baseline' not in line

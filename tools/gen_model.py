@@ -143,6 +143,122 @@ def quicksort_all_equal(n):
     return a
 
 
+def header(model):
+    """The text of include/pmg_model.h from the model dict (what tests/golden/model.json stores)."""
+    mov_link, sub, bl = model['mov_link'], model['sub'], model['bullet_links']
+    jparent, jxyz, jR, jaxis, jtype, jlo, jhi, jdamp = (model[k] for k in ('jparent', 'jxyz', 'jR', 'jaxis', 'jtype', 'jlo', 'jhi', 'jdamp'))
+    nsub = max(len(v) for v in sub.values())
+
+    def arr(x):
+        if isinstance(x, (list, tuple)):
+            return '{' + ', '.join(arr(v) for v in x) + '}'
+        if isinstance(x, int):
+            return str(x)
+        return repr(float(x))
+
+    H = []
+    H.append('/* GENERATED by tools/gen_model.py from the reference URDF/STL asset numbers -- do not edit.\n'
+             ' * Pure data shared by oracle/ and the HIP kernels (see tools/gen_model.py for sources\n'
+             ' * and the [BULLET-PRIOR] inertia rules).  All lengths m, masses kg, SI throughout. */')
+    H.append('#ifndef PMG_MODEL_H\n#define PMG_MODEL_H')
+    H.append('#define PMG_NJ 9            /* movable joints: iiwa_joint_1..7, finger1, finger2 */')
+    H.append('#define PMG_NARM 7')
+    H.append('#define PMG_NSUB %d         /* max rigid sub-bodies carried by one movable link */' % nsub)
+    H.append('#define PMG_JPARENT ' + arr(jparent))
+    H.append('#define PMG_JTYPE ' + arr(jtype) + '   /* 0 revolute, 1 prismatic */')
+    H.append('#define PMG_JXYZ ' + arr(jxyz) + '   /* joint origin in parent movable-link frame */')
+    H.append('#define PMG_JROT ' + arr(jR) + '   /* joint frame rotation (parent <- child at q=0), exact 0/+-1 */')
+    H.append('#define PMG_JAXIS ' + arr(jaxis))
+    H.append('#define PMG_JLO ' + arr(jlo))
+    H.append('#define PMG_JHI ' + arr(jhi))
+    H.append('#define PMG_JDAMP ' + arr(jdamp))
+    cnt, sm, sc, si = [], [], [], []
+    for m in mov_link:
+        s = sub[m]
+        cnt.append(len(s))
+        pad = nsub - len(s)
+        sm.append([x['mass'] for x in s] + [0.0] * pad)
+        sc.append([x['com'] for x in s] + [[0.0, 0.0, 0.0]] * pad)
+        si.append([x['inertia'] for x in s] + [[0.0, 0.0, 0.0]] * pad)
+    H.append('#define PMG_SUB_COUNT ' + arr(cnt))
+    H.append('#define PMG_SUB_MASS ' + arr(sm))
+    H.append('#define PMG_SUB_COM ' + arr(sc) + '   /* in the movable link frame */')
+    H.append('#define PMG_SUB_INERTIA ' + arr(si) + '   /* principal, link-aligned, about the sub-body COM */')
+    # ---- merged movable bodies (what the HIP kernels use): fixed children folded in ----
+    mb_mass, mb_h, mb_ilo, mb_dsum, mb_sm, mb_sc = [], [], [], [], [], []
+    for m in mov_link:
+        M = 0.0; h = np.zeros(3); I = np.zeros((3, 3)); D = np.zeros(3); sm = []; scs = []
+        for x in sub[m]:
+            l = np.array(x['com']); ms = x['mass']
+            M += ms; h += ms * l
+            I += np.diag(x['inertia']) + ms * (l @ l * np.eye(3) - np.outer(l, l))
+            D += np.array(x['inertia'])
+            if ms > 0:
+                sm.append(ms); scs.append(l.tolist())
+        assert len(sm) <= 2
+        while len(sm) < 2:
+            sm.append(0.0); scs.append([0.0, 0.0, 0.0])
+        mb_mass.append(M); mb_h.append(h.tolist())
+        mb_ilo.append([I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]])
+        mb_dsum.append(D.tolist()); mb_sm.append(sm); mb_sc.append(scs)
+    H.append('#define PMG_MB_MASS ' + arr(mb_mass) + '   /* merged movable bodies */')
+    H.append('#define PMG_MB_H ' + arr(mb_h) + '   /* first moment sum(m_s l_s), link frame */')
+    H.append('#define PMG_MB_ILO ' + arr(mb_ilo) + '   /* inertia about the link origin, link axes: xx xy xz yy yz zz */')
+    H.append('#define PMG_MB_DSUM ' + arr(mb_dsum) + '   /* sum of sub-body principal inertias (angular damping) */')
+    H.append('#define PMG_MB_SUBM_MASS ' + arr(mb_sm) + '   /* massive sub-bodies (linear damping) */')
+    H.append('#define PMG_MB_SUBM_COM ' + arr(mb_sc))
+    H.append('#define PMG_TIP_OFF ' + arr(model['tip_off']) + '   /* iiwa_gripper_tip in link_7 frame */')
+    H.append('#define PMG_GBASE_OFF ' + arr(model['gbase_off']))
+    H.append('#define PMG_TAB1_OFF ' + arr(model['tab1_off']) + '   /* in finger1 frame */')
+    H.append('#define PMG_TAB2_OFF ' + arr(model['tab2_off']))
+    H.append('#define PMG_FINGER_HALF ' + arr(model['finger_half']))
+    H.append('#define PMG_GBASE_RADIUS 0.05\n#define PMG_GBASE_HALFLEN 0.02')
+    H.append('#define PMG_FINGER_FRICTION %r' % model['finger_friction'])
+    H.append('#define PMG_ROW_ORDER ' + arr(model['row_order']) +
+             '   /* btAlignedObjectArray::quickSort permutation of [limit j0..8, motor j0..8] */')
+    H.append('#define PMG_BL_N %d   /* PyBullet link list (getNumJoints), fixed joints kept */' % len(bl))
+    H.append('#define PMG_BL_PARENT ' + arr([b['parent'] for b in bl]))
+    H.append('#define PMG_BL_TYPE ' + arr([b['type'] for b in bl]) + '   /* 0 revolute, 1 prismatic, 2 fixed */')
+    H.append('#define PMG_BL_DOF ' + arr([b['dof'] for b in bl]))
+    H.append('#define PMG_BL_XYZ ' + arr([b['xyz'] for b in bl]))
+    H.append('#define PMG_BL_ROT ' + arr([b['R'] for b in bl]))
+    H.append('#define PMG_BL_AXIS ' + arr([b['axis'] for b in bl]))
+    H.append('#define PMG_BL_MASS ' + arr([b['mass'] for b in bl]))
+    H.append('#define PMG_BL_COM ' + arr([b['com'] for b in bl]))
+    H.append('#define PMG_BL_INERTIA ' + arr([b['inertia'] for b in bl]))
+    H.append('#define PMG_BL_TIP 8\n#define PMG_BL_GBASE 12\n#define PMG_BL_FINGER1 13\n#define PMG_BL_TAB1 14\n#define PMG_BL_FINGER2 15\n#define PMG_BL_TAB2 16')
+    for k in ['plane', 'table', 'long_table', 'block', 'puck']:
+        o = model[k]
+        K = k.upper()
+        H.append('#define PMG_%s_HALF %s' % (K, arr([x / 2 for x in o['ext']])))
+        H.append('#define PMG_%s_FRICTION %r' % (K, o['friction']))
+        if o['mass'] > 0:
+            H.append('#define PMG_%s_MASS %r' % (K, o['mass']))
+            H.append('#define PMG_%s_INERTIA %s' % (K, arr(o['inertia'])))
+    ch = model['chest']
+    H.append('/* chests, index 0 = front sliding door (chest_push), 1 = up sliding lid (chest_pick_and_place); positions relative\n'
+             ' * to the chest base (kuka_multi_step_base_env.py:64), walls padded to 4 with zero-size boxes */')
+    H.append('#define PMG_CHEST_BASE {-0.7, 0.0, 0.21}')
+    H.append('#define PMG_CHEST_NWALL ' + arr([len(c_['walls']) for c_ in ch]))
+    pad = lambda w: w + [dict(c=[0.0, 0.0, -10.0], half=[0.0, 0.0, 0.0])] * (4 - len(w))
+    H.append('#define PMG_CHEST_WALL_C ' + arr([[w['c'] for w in pad(c_['walls'])] for c_ in ch]))
+    H.append('#define PMG_CHEST_WALL_HALF ' + arr([[w['half'] for w in pad(c_['walls'])] for c_ in ch]))
+    H.append('#define PMG_CHEST_DOOR_C ' + arr([c_['door_c'] for c_ in ch]) + '   /* door box centre at q = 0 */')
+    H.append('#define PMG_CHEST_DOOR_HALF ' + arr([c_['door_half'] for c_ in ch]))
+    H.append('#define PMG_CHEST_DOOR_AXIS ' + arr([c_['axis'] for c_ in ch]))
+    H.append('#define PMG_CHEST_DOOR_UPPER ' + arr([c_['upper'] for c_ in ch]))
+    H.append('#define PMG_CHEST_DOOR_MASS ' + arr([c_['mass'] for c_ in ch]) + '   /* door + handle (fixed joint) */')
+    H.append('#define PMG_CHEST_HANDLE_C ' + arr([c_['handle_c'] for c_ in ch]) + '   /* cylinder centre relative to the door centre */')
+    H.append('#define PMG_CHEST_HANDLE_R ' + arr([c_['handle_R'] for c_ in ch]) + '   /* rpy (0, 1.57, 0): the axis is the third column */')
+    H.append('#define PMG_CHEST_HANDLE_RADIUS ' + arr([c_['handle_radius'] for c_ in ch]))
+    H.append('#define PMG_CHEST_HANDLE_HALFLEN ' + arr([c_['handle_halflen'] for c_ in ch]))
+    H.append('#define PMG_CHEST_HANDLE_FRICTION %r' % ch[0]['handle_friction'])
+    H.append('#define PMG_CHEST_WALL_FRICTION 0.5   /* no <contact> tag: [BULLET-PRIOR] btCollisionObject default */')
+    H.append('#define PMG_CHEST_KEYPOINTS ' + arr([c_['keypoints'] for c_ in ch]) + '   /* left, right, handle (chest.py:34-38), relative to the door centre */')
+    H.append('#endif')
+    return '\n'.join(H) + '\n'
+
+
 def main():
     links, joints = parse_robot()
     movable = ['iiwa_joint_%d' % i for i in range(1, 8)] + ['iiwa_gripper_finger1_joint', 'iiwa_gripper_finger2_joint']
@@ -309,115 +425,8 @@ def main():
     with open(OUT_J, 'w') as f:
         json.dump(model, f, indent=1, sort_keys=True)
 
-    def arr(x):
-        if isinstance(x, (list, tuple)):
-            return '{' + ', '.join(arr(v) for v in x) + '}'
-        if isinstance(x, int):
-            return str(x)
-        return repr(float(x))
-
-    H = []
-    H.append('/* GENERATED by tools/gen_model.py from the reference URDF/STL asset numbers -- do not edit.\n'
-             ' * Pure data shared by oracle/ and the HIP kernels (see tools/gen_model.py for sources\n'
-             ' * and the [BULLET-PRIOR] inertia rules).  All lengths m, masses kg, SI throughout. */')
-    H.append('#ifndef PMG_MODEL_H\n#define PMG_MODEL_H')
-    H.append('#define PMG_NJ 9            /* movable joints: iiwa_joint_1..7, finger1, finger2 */')
-    H.append('#define PMG_NARM 7')
-    H.append('#define PMG_NSUB %d         /* max rigid sub-bodies carried by one movable link */' % nsub)
-    H.append('#define PMG_JPARENT ' + arr(jparent))
-    H.append('#define PMG_JTYPE ' + arr(jtype) + '   /* 0 revolute, 1 prismatic */')
-    H.append('#define PMG_JXYZ ' + arr(jxyz) + '   /* joint origin in parent movable-link frame */')
-    H.append('#define PMG_JROT ' + arr(jR) + '   /* joint frame rotation (parent <- child at q=0), exact 0/+-1 */')
-    H.append('#define PMG_JAXIS ' + arr(jaxis))
-    H.append('#define PMG_JLO ' + arr(jlo))
-    H.append('#define PMG_JHI ' + arr(jhi))
-    H.append('#define PMG_JDAMP ' + arr(jdamp))
-    cnt, sm, sc, si = [], [], [], []
-    for m in mov_link:
-        s = sub[m]
-        cnt.append(len(s))
-        pad = nsub - len(s)
-        sm.append([x['mass'] for x in s] + [0.0] * pad)
-        sc.append([x['com'] for x in s] + [[0.0, 0.0, 0.0]] * pad)
-        si.append([x['inertia'] for x in s] + [[0.0, 0.0, 0.0]] * pad)
-    H.append('#define PMG_SUB_COUNT ' + arr(cnt))
-    H.append('#define PMG_SUB_MASS ' + arr(sm))
-    H.append('#define PMG_SUB_COM ' + arr(sc) + '   /* in the movable link frame */')
-    H.append('#define PMG_SUB_INERTIA ' + arr(si) + '   /* principal, link-aligned, about the sub-body COM */')
-    # ---- merged movable bodies (what the HIP kernels use): fixed children folded in ----
-    mb_mass, mb_h, mb_ilo, mb_dsum, mb_sm, mb_sc = [], [], [], [], [], []
-    for m in mov_link:
-        M = 0.0; h = np.zeros(3); I = np.zeros((3, 3)); D = np.zeros(3); sm = []; scs = []
-        for x in sub[m]:
-            l = np.array(x['com']); ms = x['mass']
-            M += ms; h += ms * l
-            I += np.diag(x['inertia']) + ms * (l @ l * np.eye(3) - np.outer(l, l))
-            D += np.array(x['inertia'])
-            if ms > 0:
-                sm.append(ms); scs.append(l.tolist())
-        assert len(sm) <= 2
-        while len(sm) < 2:
-            sm.append(0.0); scs.append([0.0, 0.0, 0.0])
-        mb_mass.append(M); mb_h.append(h.tolist())
-        mb_ilo.append([I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]])
-        mb_dsum.append(D.tolist()); mb_sm.append(sm); mb_sc.append(scs)
-    H.append('#define PMG_MB_MASS ' + arr(mb_mass) + '   /* merged movable bodies */')
-    H.append('#define PMG_MB_H ' + arr(mb_h) + '   /* first moment sum(m_s l_s), link frame */')
-    H.append('#define PMG_MB_ILO ' + arr(mb_ilo) + '   /* inertia about the link origin, link axes: xx xy xz yy yz zz */')
-    H.append('#define PMG_MB_DSUM ' + arr(mb_dsum) + '   /* sum of sub-body principal inertias (angular damping) */')
-    H.append('#define PMG_MB_SUBM_MASS ' + arr(mb_sm) + '   /* massive sub-bodies (linear damping) */')
-    H.append('#define PMG_MB_SUBM_COM ' + arr(mb_sc))
-    H.append('#define PMG_TIP_OFF ' + arr(model['tip_off']) + '   /* iiwa_gripper_tip in link_7 frame */')
-    H.append('#define PMG_GBASE_OFF ' + arr(model['gbase_off']))
-    H.append('#define PMG_TAB1_OFF ' + arr(model['tab1_off']) + '   /* in finger1 frame */')
-    H.append('#define PMG_TAB2_OFF ' + arr(model['tab2_off']))
-    H.append('#define PMG_FINGER_HALF ' + arr(model['finger_half']))
-    H.append('#define PMG_GBASE_RADIUS 0.05\n#define PMG_GBASE_HALFLEN 0.02')
-    H.append('#define PMG_FINGER_FRICTION %r' % model['finger_friction'])
-    H.append('#define PMG_ROW_ORDER ' + arr(model['row_order']) +
-             '   /* btAlignedObjectArray::quickSort permutation of [limit j0..8, motor j0..8] */')
-    H.append('#define PMG_BL_N %d   /* PyBullet link list (getNumJoints), fixed joints kept */' % len(bl))
-    H.append('#define PMG_BL_PARENT ' + arr([b['parent'] for b in bl]))
-    H.append('#define PMG_BL_TYPE ' + arr([b['type'] for b in bl]) + '   /* 0 revolute, 1 prismatic, 2 fixed */')
-    H.append('#define PMG_BL_DOF ' + arr([b['dof'] for b in bl]))
-    H.append('#define PMG_BL_XYZ ' + arr([b['xyz'] for b in bl]))
-    H.append('#define PMG_BL_ROT ' + arr([b['R'] for b in bl]))
-    H.append('#define PMG_BL_AXIS ' + arr([b['axis'] for b in bl]))
-    H.append('#define PMG_BL_MASS ' + arr([b['mass'] for b in bl]))
-    H.append('#define PMG_BL_COM ' + arr([b['com'] for b in bl]))
-    H.append('#define PMG_BL_INERTIA ' + arr([b['inertia'] for b in bl]))
-    H.append('#define PMG_BL_TIP 8\n#define PMG_BL_GBASE 12\n#define PMG_BL_FINGER1 13\n#define PMG_BL_TAB1 14\n#define PMG_BL_FINGER2 15\n#define PMG_BL_TAB2 16')
-    for k in ['plane', 'table', 'long_table', 'block', 'puck']:
-        o = model[k]
-        K = k.upper()
-        H.append('#define PMG_%s_HALF %s' % (K, arr([x / 2 for x in o['ext']])))
-        H.append('#define PMG_%s_FRICTION %r' % (K, o['friction']))
-        if o['mass'] > 0:
-            H.append('#define PMG_%s_MASS %r' % (K, o['mass']))
-            H.append('#define PMG_%s_INERTIA %s' % (K, arr(o['inertia'])))
-    ch = model['chest']
-    H.append('/* chests, index 0 = front sliding door (chest_push), 1 = up sliding lid (chest_pick_and_place); positions relative\n'
-             ' * to the chest base (kuka_multi_step_base_env.py:64), walls padded to 4 with zero-size boxes */')
-    H.append('#define PMG_CHEST_BASE {-0.7, 0.0, 0.21}')
-    H.append('#define PMG_CHEST_NWALL ' + arr([len(c_['walls']) for c_ in ch]))
-    pad = lambda w: w + [dict(c=[0.0, 0.0, -10.0], half=[0.0, 0.0, 0.0])] * (4 - len(w))
-    H.append('#define PMG_CHEST_WALL_C ' + arr([[w['c'] for w in pad(c_['walls'])] for c_ in ch]))
-    H.append('#define PMG_CHEST_WALL_HALF ' + arr([[w['half'] for w in pad(c_['walls'])] for c_ in ch]))
-    H.append('#define PMG_CHEST_DOOR_C ' + arr([c_['door_c'] for c_ in ch]) + '   /* door box centre at q = 0 */')
-    H.append('#define PMG_CHEST_DOOR_HALF ' + arr([c_['door_half'] for c_ in ch]))
-    H.append('#define PMG_CHEST_DOOR_AXIS ' + arr([c_['axis'] for c_ in ch]))
-    H.append('#define PMG_CHEST_DOOR_UPPER ' + arr([c_['upper'] for c_ in ch]))
-    H.append('#define PMG_CHEST_DOOR_MASS ' + arr([c_['mass'] for c_ in ch]) + '   /* door + handle (fixed joint) */')
-    H.append('#define PMG_CHEST_HANDLE_C ' + arr([c_['handle_c'] for c_ in ch]) + '   /* cylinder centre relative to the door centre */')
-    H.append('#define PMG_CHEST_HANDLE_R ' + arr([c_['handle_R'] for c_ in ch]) + '   /* rpy (0, 1.57, 0): the axis is the third column */')
-    H.append('#define PMG_CHEST_HANDLE_RADIUS ' + arr([c_['handle_radius'] for c_ in ch]))
-    H.append('#define PMG_CHEST_HANDLE_HALFLEN ' + arr([c_['handle_halflen'] for c_ in ch]))
-    H.append('#define PMG_CHEST_HANDLE_FRICTION %r' % ch[0]['handle_friction'])
-    H.append('#define PMG_CHEST_WALL_FRICTION 0.5   /* no <contact> tag: [BULLET-PRIOR] btCollisionObject default */')
-    H.append('#define PMG_CHEST_KEYPOINTS ' + arr([c_['keypoints'] for c_ in ch]) + '   /* left, right, handle (chest.py:34-38), relative to the door centre */')
-    H.append('#endif')
     with open(OUT_H, 'w') as f:
-        f.write('\n'.join(H) + '\n')
+        f.write(header(model))
     print('wrote', OUT_H, OUT_J)
     for m in mov_link:
         print(m, [(s['name'], s['mass'], [round(x, 5) for x in s['inertia']]) for s in sub[m]])

@@ -26,16 +26,16 @@ bash tools/profile.sh pick_and_place $tag 8192 > /dev/null 2>&1
 cp gpurun_out/profiles/${tag}_pick_and_place8192_* $out/ 2>/dev/null
 cp gpurun_out/profiles/${tag}_pick_and_place8192_* profiles/ 2>/dev/null
 # 3. the bench lines (headline = the default command)
-python bench.py > $out/${tag}_bench_reach4096.json 2>/dev/null
+python bench.py --full > $out/${tag}_bench_reach4096.json 2>/dev/null
 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_reach4096_driver_command.json 2>/dev/null
 for t in $tasks; do
   [ $t = reach ] && continue
-  python bench.py --task $t --steps 100 --warmup 10 > $out/${tag}_bench_${t}4096.json 2>/dev/null
+  python bench.py --task $t --steps 100 --warmup 10 --full > $out/${tag}_bench_${t}4096.json 2>/dev/null
 done
-python bench.py --task pick_and_place --envs-per-gpu 8192 --dense-reward --steps 100 --warmup 10 > $out/${tag}_bench_pick_and_place8192_dense.json 2>/dev/null
-python bench.py --task pick_and_place --envs-per-gpu 8192 --steps 100 --warmup 10 --no-cpu-baseline > $out/${tag}_bench_pick_and_place8192_binary.json 2>/dev/null
+python bench.py --task pick_and_place --envs-per-gpu 8192 --dense-reward --steps 100 --warmup 10 --full > $out/${tag}_bench_pick_and_place8192_dense.json 2>/dev/null
+python bench.py --task pick_and_place --envs-per-gpu 8192 --steps 100 --warmup 10 --full --no-cpu-baseline > $out/${tag}_bench_pick_and_place8192_binary.json 2>/dev/null
 python bench.py --episode-steps 10 --no-cpu-baseline --no-extras > $out/${tag}_bench_reach4096_short_episodes.json 2>/dev/null
-python bench.py --lockstep --no-cpu-baseline > $out/${tag}_bench_reach4096_lockstep.json 2>/dev/null
+python bench.py --lockstep --full --no-cpu-baseline > $out/${tag}_bench_reach4096_lockstep.json 2>/dev/null
 PMG_REACH_TWO_WAVES=0 python bench.py --no-cpu-baseline --no-extras > $out/${tag}_bench_reach4096_one_wave_workgroups.json 2>/dev/null
 bash tools/bench_all.sh > $out/${tag}_bench_all_tasks_staggered_and_lockstep.txt 2>&1
 PMG_PACKED=0 python bench.py --no-cpu-baseline --no-extras > $out/${tag}_bench_reach4096_one_env_per_wave.json 2>/dev/null
