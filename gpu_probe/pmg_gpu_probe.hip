@@ -1,0 +1,330 @@
+/* pmg_gpu_probe.hip -- TEST INFRASTRUCTURE: small probe kernels that run single primitives of the SHIPPED pmg_wave.h and
+ * single device functions of pmg_device.h / pmg_contact.h on a real gfx950, compiled with the product's own flags
+ * (Makefile), so that tests/test_gpu_wave_primitives.py and tests/test_gpu_device_functions.py can compare each of them
+ * with its model / the float64 oracle directly instead of through a whole rollout.  Never part of the product.
+ *
+ * Every probe is ONE workgroup, finite, and masks every index it derives from its arguments; every exported function
+ * allocates, launches on the null stream, synchronises, copies back and returns the HIP status (< 0: bad arguments).
+ * Built twice: as is (the inline-asm DPP paths that ship) and with -DPMG_NO_R0_DPP -DPMG_NO_DPP_FMAC -DPMG_NO_NEWBCAST
+ * (the plain C++ branches of the same header), same symbols, two libraries. */
+#include <hip/hip_runtime.h>
+#include <cstring>
+#include "pmg_contact.h"
+
+#define WV wv
+#define PRIM_FN prim_probe_wv
+#define PRIM_WR 0
+#include "pmg_prim_probe.inc"
+#undef WV
+#undef PRIM_FN
+#undef PRIM_WR
+#define WV wr
+#define PRIM_FN prim_probe_wr
+#define PRIM_WR 1
+#include "pmg_prim_probe.inc"
+#undef WV
+#undef PRIM_FN
+#undef PRIM_WR
+
+namespace {
+
+/* device buffers of one call: freed on every path */
+struct Dev {
+    void* p[12];
+    int n = 0;
+    hipError_t err = hipSuccess;
+    template <class T>
+    T* up(const T* h, size_t count)          /* allocate and fill from the host (h == nullptr: zeros) */
+    {
+        void* d = nullptr;
+        if (err != hipSuccess || n >= 12) { if (err == hipSuccess) err = hipErrorOutOfMemory; return nullptr; }
+        err = hipMalloc(&d, count * sizeof(T) ? count * sizeof(T) : 4);
+        if (err != hipSuccess) return nullptr;
+        p[n++] = d;
+        err = h ? hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice) : hipMemset(d, 0, count * sizeof(T));
+        return (T*)d;
+    }
+    template <class T>
+    void down(T* h, const T* d, size_t count)
+    {
+        if (err == hipSuccess) err = hipMemcpy(h, d, count * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    void sync()
+    {
+        if (err == hipSuccess) err = hipGetLastError();
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+    }
+    ~Dev() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
+};
+
+/* ---- primitives ------------------------------------------------------------------------------------------------ */
+/* wave: the wavefront of the workgroup that runs the probe (the others leave at once: the helper wavefronts of the list-0
+ * kernels).  rowsel < 0: all 64 lanes together; 0..3: that 16-lane row alone; 4: the four rows one after the other, each
+ * in its own divergent branch (the packed layout's "control flow diverges by row") */
+template <bool WR>
+__global__ void __launch_bounds__(192) k_prim(int fam, int wave, int rowsel, int src, const float* in, float* out)
+{
+    const int t = (int)threadIdx.x;
+    if ((t >> 6) != wave) return;
+    const int row = (t >> 4) & 3;
+    const int k0 = rowsel == 4 ? 0 : rowsel, k1 = rowsel == 4 ? 3 : rowsel;
+    for (int k = k0; k <= k1; k++)
+        if (k < 0 || row == k) {
+            if (WR) prim_probe_wr(fam, src, in, out);
+            else prim_probe_wv(fam, src, in, out);
+        }
+}
+
+/* ---- dynamics / IK: the bodies of pmge_probe_dynamics / pmge_probe_ik (tests/emu/pmg_probe.cpp), case after case ---- */
+#define DYN_BODY(NSP, WVN, CASE, VALID)                                                                                    \
+    {                                                                                                                     \
+        using namespace NSP;                                                                                              \
+        const int l = WVN::lane();                                                                                        \
+        const float ql = l < NJ ? q[9 * (CASE) + l] : 0.f, qdl = l < NJ ? qd[9 * (CASE) + l] : 0.f, tl = l < NJ ? tau[9 * (CASE) + l] : 0.f; \
+        Kin k;                                                                                                            \
+        fk(c, ql, k);                                                                                                     \
+        float tip[3], Rt[9];                                                                                              \
+        tip_frame(k, tip, Rt);                                                                                            \
+        float I10[10], minv[NJ];                                                                                          \
+        body_inertia(c, k, I10);                                                                                          \
+        if (l >= NJ)                                                                                                      \
+            for (int a = 0; a < 10; a++) I10[a] = 0.f;                                                                    \
+        mass_inverse(k, I10, minv);                                                                                       \
+        const float h = bias_torque(c, k, I10, qdl);                                                                      \
+        const float rq = l < NJ ? tl - h : 0.f;                                                                           \
+        float acc = 0.f;                                                                                                  \
+        for (int j = 0; j < NJ; j++) acc += minv[j] * WVN::bcast(rq, j);                                                  \
+        if ((VALID) && l < NJ) {                                                                                          \
+            qdd[9 * (CASE) + l] = acc;                                                                                    \
+            for (int j = 0; j < NJ; j++) minv_out[81 * (CASE) + 9 * l + j] = minv[j];                                     \
+        }                                                                                                                 \
+        if ((VALID) && l == 0) {                                                                                          \
+            for (int a = 0; a < 3; a++) tip_out[12 * (CASE) + a] = tip[a];                                                \
+            for (int a = 0; a < 9; a++) tip_out[12 * (CASE) + 3 + a] = Rt[a];                                             \
+        }                                                                                                                 \
+    }
+
+__global__ void __launch_bounds__(64) k_dynamics(int n, const float* q, const float* qd, const float* tau, float* qdd, float* minv_out, float* tip_out)
+{
+    __shared__ pmg::LaneTabStore lcs;
+    pmg::LaneConst c;
+    pmg::load_lane_const(lcs, c);
+    for (int i = 0; i < n; i++) DYN_BODY(pmg, wv, i, true)
+}
+/* the packed reach layout: four cases at once, one per 16-lane row */
+__global__ void __launch_bounds__(64) k_dynamics_packed(int n, const float* q, const float* qd, const float* tau, float* qdd, float* minv_out, float* tip_out)
+{
+    __shared__ pmgp::LaneTabStore lcs;
+    pmgp::LaneConst c;
+    pmgp::load_lane_const(lcs, c);
+    for (int i = 0; i < n; i += 4) {
+        const int mine = i + wr::row();
+        const bool valid = mine < n;
+        const int cs = valid ? mine : n - 1;           /* (a row without a case repeats the last one and stores nothing) */
+        DYN_BODY(pmgp, wr, cs, valid)
+    }
+}
+__global__ void __launch_bounds__(64) k_ik(int n, const float* q, const float* target, float* q_out)
+{
+    using namespace pmg;
+    __shared__ LaneTabStore lcs;
+    LaneConst c;
+    load_lane_const(lcs, c);
+    const int l = wv::lane();
+    for (int i = 0; i < n; i++) {
+        const float r = ik_solve(c, l < NJ ? q[9 * i + l] : 0.f, target + 3 * i);
+        if (l < NJ) q_out[9 * i + l] = r;
+    }
+}
+__global__ void __launch_bounds__(64) k_ik_packed(int n, const float* q, const float* target, float* q_out)
+{
+    using namespace pmgp;
+    __shared__ LaneTabStore lcs;
+    LaneConst c;
+    load_lane_const(lcs, c);
+    const int l = wr::lane();
+    for (int i = 0; i < n; i += 4) {
+        const int mine = i + wr::row();
+        const bool valid = mine < n;
+        const int cs = valid ? mine : n - 1;
+        const float r = ik_solve(c, l < NJ ? q[9 * cs + l] : 0.f, target + 3 * cs);
+        if (valid && l < NJ) q_out[9 * cs + l] = r;
+    }
+}
+
+/* ---- narrowphase: one pair per lane, every operand in LDS as in the product (tools/prof_narrow.hip's layout) ---------- */
+constexpr int PAIR_FLOATS = 30;   /* ca3 Ra9 ha3 cb3 Rb9 hb3 */
+__global__ void __launch_bounds__(64) k_narrow(int kind, int np, const float* pairs, float margin, float* outp, int* nout, float* ambp)
+{
+    __shared__ __attribute__((aligned(16))) float A[64][12], B[64][12], hA[64][4], hB[64][4], out[64][4 * pmg::CP], W[64][pmg::BOX_WORK];
+    const int l = (int)threadIdx.x & 63;
+    np = np < 64 ? np : 64;
+    if (l < np) {
+        const float* p = pairs + PAIR_FLOATS * l;
+        for (int a = 0; a < 12; a++) { A[l][a] = p[a]; B[l][a] = p[15 + a]; }
+        for (int a = 0; a < 3; a++) { hA[l][a] = p[12 + a]; hB[l][a] = p[27 + a]; }
+        for (int a = 0; a < 4 * pmg::CP; a++) out[l][a] = 0.f;
+    }
+    __syncthreads();
+    int n = 0;
+    float amb = 1e30f;
+    if (l < np) {
+        if (kind == 0) n = pmg::box_box_fast(A[l], A[l] + 3, hA[l], B[l], B[l] + 3, hB[l], margin, out[l], W[l]);
+        else if (kind == 2) n = pmg::box_box(A[l], A[l] + 3, hA[l], B[l], B[l] + 3, hB[l], margin, out[l], W[l]);
+        else if (kind == 3) n = pmg::box_box_fast<true, true>(A[l], A[l] + 3, hA[l], B[l], B[l] + 3, hB[l], margin, out[l], W[l]);
+        else n = pmg::cyl_box(A[l], A[l] + 3, hA[l][0], hA[l][2], B[l], B[l] + 3, hB[l][0], hB[l][1], hB[l][2], margin, out[l], W[l], &amb);
+    }
+    wv::lds_sync();
+    if (l < np) {
+        n = n < 0 ? 0 : (n > 4 ? 4 : n);
+        for (int a = 0; a < 4 * pmg::CP; a++) outp[4 * pmg::CP * l + a] = out[l][a];
+        nout[l] = n;
+        ambp[l] = amb;
+    }
+}
+
+/* ---- the double-precision helpers of the cylinder repeat: one case per lane ----------------------------------------- */
+__global__ void __launch_bounds__(64) k_fk64(int n, const float* q9, const int* body, double* p, double* R)
+{
+    const int l = (int)threadIdx.x & 63;
+    for (int i = l; i < n; i += 64) {
+        const int b = body[i];
+        const int bb = (b == pmg::BODY_FINGER1 || b == pmg::BODY_FINGER2) ? b : pmg::BODY_GBASE;
+        pmg::fk64_link(q9 + 9 * i, bb, p + 3 * i, R + 9 * i);
+    }
+}
+__global__ void __launch_bounds__(64) k_cyl_redo64(int n, int ck, const float* q9, const float* blk, const float* doorq, const float* kc, float prad, float phl,
+                                                   float* outp, int* nout)
+{
+    __shared__ __attribute__((aligned(16))) float out[64][4 * pmg::CP], W[64][pmg::BOX_WORK];
+    const int l = (int)threadIdx.x & 63;
+    n = n < 64 ? n : 64;
+    if (l < n) {
+        for (int a = 0; a < 4 * pmg::CP; a++) out[l][a] = 0.f;
+        int m;
+        /* the slide puck (free body 0) against the table: the pair the emulated test drives */
+        if (ck == 0) m = pmg::cyl_redo64<0>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
+        else if (ck == 1) m = pmg::cyl_redo64<1>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
+        else m = pmg::cyl_redo64<-1>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
+        m = m < 0 ? 0 : (m > 4 ? 4 : m);
+        for (int a = 0; a < 4 * pmg::CP; a++) outp[4 * pmg::CP * l + a] = out[l][a];
+        nout[l] = m;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+/* which build this is: 0 = the shipped paths, 1 = the plain C++ branches */
+int pmgd_variant()
+{
+#if defined(PMG_NO_R0_DPP) && defined(PMG_NO_DPP_FMAC) && defined(PMG_NO_NEWBCAST)
+    return 1;
+#else
+    return 0;
+#endif
+}
+int pmgd_prim_nin() { return prim::NIN; }
+int pmgd_prim_nout() { return prim::NOUT; }
+int pmgd_prim_families() { return prim::F_COUNT; }
+
+/* in [NIN][64], out [NOUT][64] (in and out: the caller's sentinel stays where the probe writes nothing) */
+int pmgd_prim(int wr_ns, int fam, int threads, int wave, int rowsel, int src, const float* in, float* out)
+{
+    if ((threads != 64 && threads != 128 && threads != 192) || wave < 0 || wave >= threads / 64 || fam < 0 || fam >= prim::F_COUNT || rowsel < -1 || rowsel > 4)
+        return -1;
+    Dev d;
+    const float* din = d.up(in, (size_t)prim::NIN * 64);
+    float* dout = d.up(out, (size_t)prim::NOUT * 64);
+    if (d.err == hipSuccess) {
+        if (wr_ns) hipLaunchKernelGGL(k_prim<true>, dim3(1), dim3(threads), 0, 0, fam, wave, rowsel, src & 63, din, dout);
+        else hipLaunchKernelGGL(k_prim<false>, dim3(1), dim3(threads), 0, 0, fam, wave, rowsel, src & 63, din, dout);
+    }
+    d.sync();
+    d.down(out, dout, (size_t)prim::NOUT * 64);
+    return (int)d.err;
+}
+
+/* n cases: q, qd, tau [n][9] -> qdd [n][9], minv [n][81], tip [n][12] (position, rotation of the tip frame) */
+int pmgd_dynamics(int packed, int n, const float* q, const float* qd, const float* tau, float* qdd, float* minv_out, float* tip_out)
+{
+    if (n < 1 || n > 4096) return -1;
+    Dev d;
+    const float *dq = d.up(q, 9 * (size_t)n), *dqd = d.up(qd, 9 * (size_t)n), *dt = d.up(tau, 9 * (size_t)n);
+    float *da = d.up<float>(nullptr, 9 * (size_t)n), *dm = d.up<float>(nullptr, 81 * (size_t)n), *dp = d.up<float>(nullptr, 12 * (size_t)n);
+    if (d.err == hipSuccess) {
+        if (packed) hipLaunchKernelGGL(k_dynamics_packed, dim3(1), dim3(64), 0, 0, n, dq, dqd, dt, da, dm, dp);
+        else hipLaunchKernelGGL(k_dynamics, dim3(1), dim3(64), 0, 0, n, dq, dqd, dt, da, dm, dp);
+    }
+    d.sync();
+    d.down(qdd, da, 9 * (size_t)n); d.down(minv_out, dm, 81 * (size_t)n); d.down(tip_out, dp, 12 * (size_t)n);
+    return (int)d.err;
+}
+int pmgd_ik(int packed, int n, const float* q, const float* target, float* q_out)
+{
+    if (n < 1 || n > 4096) return -1;
+    Dev d;
+    const float *dq = d.up(q, 9 * (size_t)n), *dt = d.up(target, 3 * (size_t)n);
+    float* dout = d.up<float>(nullptr, 9 * (size_t)n);
+    if (d.err == hipSuccess) {
+        if (packed) hipLaunchKernelGGL(k_ik_packed, dim3(1), dim3(64), 0, 0, n, dq, dt, dout);
+        else hipLaunchKernelGGL(k_ik, dim3(1), dim3(64), 0, 0, n, dq, dt, dout);
+    }
+    d.sync();
+    d.down(q_out, dout, 9 * (size_t)n);
+    return (int)d.err;
+}
+
+/* n pairs [n][30] (ca3 Ra9 ha3 cb3 Rb9 hb3; a cylinder A: ha = r, r, half length), `lanes` (1..64) of them per launch, one
+ * per lane.  kind 0: box_box_fast, 1: cyl_box, 2: box_box, 3: box_box_fast<true, true>.  -> out [n][40], nout [n], amb [n] */
+int pmgd_narrowphase(int kind, int n, int lanes, const float* pairs, float margin, float* out, int* nout, float* amb)
+{
+    if (kind < 0 || kind > 3 || n < 1 || n > 65536 || lanes < 1 || lanes > 64) return -1;
+    Dev d;
+    const float* dp = d.up(pairs, (size_t)PAIR_FLOATS * n);
+    float *dout = d.up<float>(nullptr, 40 * (size_t)n), *damb = d.up<float>(nullptr, (size_t)n);
+    int* dn = d.up<int>(nullptr, (size_t)n);
+    for (int i = 0; i < n && d.err == hipSuccess; i += lanes) {
+        const int np = n - i < lanes ? n - i : lanes;
+        hipLaunchKernelGGL(k_narrow, dim3(1), dim3(64), 0, 0, kind, np, dp + (size_t)PAIR_FLOATS * i, margin, dout + 40 * (size_t)i, dn + i, damb + i);
+        d.err = hipGetLastError();
+    }
+    d.sync();
+    d.down(out, dout, 40 * (size_t)n); d.down(nout, dn, (size_t)n); d.down(amb, damb, (size_t)n);
+    return (int)d.err;
+}
+
+/* fk64_link: q9 [n][9], body [n] (BODY_FINGER1 / 2, anything else: the gripper base) -> p [n][3], R [n][9] (double) */
+int pmgd_fk64(int n, const float* q9, const int* body, double* p, double* R)
+{
+    if (n < 1 || n > 65536) return -1;
+    Dev d;
+    const float* dq = d.up(q9, 9 * (size_t)n);
+    const int* db = d.up(body, (size_t)n);
+    double *dp = d.up<double>(nullptr, 3 * (size_t)n), *dR = d.up<double>(nullptr, 9 * (size_t)n);
+    if (d.err == hipSuccess) hipLaunchKernelGGL(k_fk64, dim3(1), dim3(64), 0, 0, n, dq, db, dp, dR);
+    d.sync();
+    d.down(p, dp, 3 * (size_t)n); d.down(R, dR, 9 * (size_t)n);
+    return (int)d.err;
+}
+/* cyl_redo64<ck> of the puck (free body 0 of each case's state row) against the table: q9 [n][9], blk [n][13], doorq [n],
+ * kc [24] -> out [n][40], nout [n] */
+int pmgd_cyl_redo64(int n, int ck, const float* q9, const float* blk, const float* doorq, const float* kc, float prad, float phl, float* out, int* nout)
+{
+    if (n < 1 || n > 65536 || ck < -1 || ck > 1) return -1;
+    Dev d;
+    const float *dq = d.up(q9, 9 * (size_t)n), *db = d.up(blk, 13 * (size_t)n), *dd = d.up(doorq, (size_t)n), *dk = d.up(kc, 24);
+    float* dout = d.up<float>(nullptr, 40 * (size_t)n);
+    int* dn = d.up<int>(nullptr, (size_t)n);
+    for (int i = 0; i < n && d.err == hipSuccess; i += 64) {
+        const int np = n - i < 64 ? n - i : 64;
+        hipLaunchKernelGGL(k_cyl_redo64, dim3(1), dim3(64), 0, 0, np, ck, dq + 9 * (size_t)i, db + 13 * (size_t)i, dd + i, dk, prad, phl, dout + 40 * (size_t)i, dn + i);
+        d.err = hipGetLastError();
+    }
+    d.sync();
+    d.down(out, dout, 40 * (size_t)n); d.down(nout, dn, (size_t)n);
+    return (int)d.err;
+}
+
+}  // extern "C"

@@ -9,6 +9,12 @@
  *   - DPP butterfly + 4 readlanes for full-wave sums and maxima,
  * never through memory.  (tests/emu/pmg_wave.h is the CPU stand-in the
  * test-only emulator uses; this file is the only one that ships.)
+ *
+ * Tested ON THE DEVICE, primitive by primitive: gpu_probe/ builds this header with the product's flags and
+ * tests/test_gpu_wave_primitives.py compares every primitive whose result is data -- every template argument, full
+ * wavefront / one row at a time / helper wavefronts, the inline-asm paths and the plain C++ branches -- with the numpy
+ * models of tests/wave_models.py, which are written from the comments below: a comment here is a contract.  The
+ * emulator's stand-in is held to the same models (tests/test_wave_primitive_models.py).
  */
 #ifndef PMG_WAVE_H
 #define PMG_WAVE_H
@@ -296,6 +302,8 @@ __device__ __forceinline__ float dot6_lanes_r0(const float* c, float v)
     return acc;
 #endif
 }
+template <int N>
+__device__ __forceinline__ float row_shr(float v, float fill);   /* (defined below; the plain branch of add_shr2_bank2 uses it) */
 /* lanes 8..11 of every row: y <- y(lane l - 2) + x; the other lanes keep y (the finger-2 step of chain_prefix) */
 __device__ __forceinline__ float add_shr2_bank2(float y, float x)
 {

@@ -6,6 +6,44 @@
 #include <vector>
 #include "pmg_kernels.h"
 
+/* the primitive probes of the device probe library (gpu_probe/), here against the emulator's stand-in header */
+#define WV wv
+#define PRIM_FN prim_probe_wv
+#define PRIM_WR 0
+#include "../../gpu_probe/pmg_prim_probe.inc"
+#undef WV
+#undef PRIM_FN
+#undef PRIM_WR
+#define WV wr
+#define PRIM_FN prim_probe_wr
+#define PRIM_WR 1
+#include "../../gpu_probe/pmg_prim_probe.inc"
+#undef WV
+#undef PRIM_FN
+#undef PRIM_WR
+
+/* same arguments and lane contexts as pmgd_prim (gpu_probe/pmg_gpu_probe.hip) */
+extern "C" int pmge_prim(int wr_ns, int fam, int threads, int wave, int rowsel, int src, const float* in, float* out)
+{
+    if ((threads != 64 && threads != 128 && threads != 192) || wave < 0 || wave >= threads / 64 || fam < 0 || fam >= prim::F_COUNT || rowsel < -1 || rowsel > 4)
+        return -1;
+    emu::launch(1, threads, [&]() {
+        const int t = (int)threadIdx.x;
+        if ((t >> 6) != wave) return;
+        const int row = (t >> 4) & 3;
+        const int k0 = rowsel == 4 ? 0 : rowsel, k1 = rowsel == 4 ? 3 : rowsel;
+        for (int k = k0; k <= k1; k++)
+            if (k < 0 || row == k) {
+                if (wr_ns) prim_probe_wr(fam, src & 63, in, out);
+                else prim_probe_wv(fam, src & 63, in, out);
+            }
+    });
+    return 0;
+}
+extern "C" int pmge_prim_nin() { return prim::NIN; }
+extern "C" int pmge_prim_nout() { return prim::NOUT; }
+extern "C" int pmge_prim_families() { return prim::F_COUNT; }
+
 extern "C" void pmge_probe_dynamics(const float* q, const float* qd, const float* tau, float* qdd, float* minv_out,
                                     float* tip_out)
 {

@@ -1,5 +1,6 @@
 /* CPU stand-in of pybullet_multigoal_gym_amd/csrc/pmg_wave.h for the fiber emulator
- * (TEST INFRASTRUCTURE).  Same API, lane exchange through a shared buffer. */
+ * (TEST INFRASTRUCTURE).  Same API, lane exchange through a shared buffer.  Held to the same numpy models as the
+ * shipped header (tests/wave_models.py: tests/test_wave_primitive_models.py here, tests/test_gpu_wave_primitives.py there). */
 #ifndef PMG_WAVE_H
 #define PMG_WAVE_H
 #include "hip_emu.h"
@@ -242,6 +243,8 @@ inline float bcast(float v, int src)
 inline int bcast_i(int v, int src) { return __float_as_int(bcast(__int_as_float(v), src)); }
 template <int SRC>
 inline float bcast_c(float v) { return bcast(v, SRC); }
+template <int SRC>
+inline int bcast_ci(int v) { return bcast_i(v, SRC); }
 template <int N>
 inline float row_shr(float v, float fill) { return wv::row_shr<N>(v, fill); }
 template <int N>

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import device_cases as D
 import oracle_lib as O
 import pybullet_multigoal_gym_amd as pmg
 
@@ -16,31 +17,70 @@ def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def test_device_dynamics_functions_match_oracle(emu_library):
-    lib = C.CDLL(emu_library.path)
-    rs = np.random.RandomState(0)
-    for _ in range(3):
-        q = np.float32(np.r_[rs.uniform(-1, 1, 7) + [0, -0.5, 0, 1.7, 0, -0.8, 0], rs.uniform(0, 0.035, 2)])
-        qd = np.float32(np.r_[rs.uniform(-2, 2, 7), rs.uniform(-0.1, 0.1, 2)])
-        tau = np.float32(rs.uniform(-1, 1, 9))
-        qdd, mi, tip = np.zeros(9, np.float32), np.zeros(81, np.float32), np.zeros(12, np.float32)
-        lib.pmge_probe_dynamics(_fp(q), _fp(qd), _fp(tau), _fp(qdd), _fp(mi), _fp(tip))
-        ref = O.fdyn(q.astype(float), qd.astype(float), tau.astype(float))
-        assert np.abs(qdd - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
-        mref = O.minv(q.astype(float))
-        assert np.abs(mi.reshape(9, 9) - mref).max() < 1e-5 * np.abs(mref).max()    # float32 Gauss-Jordan, cond(M) ~ 1e3
-        p, R = O.fk_tip(q.astype(float))
-        assert np.abs(tip[:3] - p).max() < 1e-6 and np.abs(tip[3:].reshape(3, 3) - R).max() < 1e-6
+class EmuRunners:
+    """the runners of tests/device_cases.py on the emulator build: one host call per case"""
+
+    def __init__(self, emu_library):
+        self.lib = lib = C.CDLL(emu_library.path)
+        lib.pmge_probe_narrowphase.restype = C.c_int
+        lib.pmge_probe_cyl_redo64.restype = C.c_int
+        lib.pmge_probe_cyl_amb.restype = C.c_int
+
+    def dynamics(self, q, qd, tau):
+        n = len(q)
+        qdd, mi, tip = np.zeros((n, 9), np.float32), np.zeros((n, 81), np.float32), np.zeros((n, 12), np.float32)
+        for i in range(n):
+            self.lib.pmge_probe_dynamics(_fp(q[i]), _fp(qd[i]), _fp(tau[i]), _fp(qdd[i]), _fp(mi[i]), _fp(tip[i]))
+        return qdd, mi, tip
+
+    def ik(self, q, target):
+        out = np.zeros((len(q), 9), np.float32)
+        for i in range(len(q)):
+            self.lib.pmge_probe_ik(_fp(q[i]), _fp(target[i]), _fp(out[i]))
+        return out
+
+    def narrowphase(self, kind, pairs, with_amb=False):
+        n, out, amb = np.zeros(len(pairs), np.int32), np.zeros((len(pairs), 40), np.float32), np.full(len(pairs), 1e30, np.float32)
+        for i, p in enumerate(np.ascontiguousarray(pairs, np.float32)):
+            a = [np.ascontiguousarray(x) for x in D.unpack_pair(p)]
+            if with_amb:
+                v = C.c_float(0)
+                n[i] = self.lib.pmge_probe_cyl_amb(_fp(a[0]), _fp(a[1]), C.c_float(a[2][0]), C.c_float(a[2][2]), _fp(a[3]), _fp(a[4]), _fp(a[5]), C.c_float(0.002),
+                                                   _fp(out[i]), C.byref(v))
+                amb[i] = v.value
+            else:
+                n[i] = self.lib.pmge_probe_narrowphase(kind, *[_fp(x) for x in a], C.c_float(0.002), _fp(out[i]))
+        return n, out, amb
+
+    def narrowphase_amb(self, kind, pairs):
+        assert kind == D.NP_CYL
+        return self.narrowphase(kind, pairs, with_amb=True)
+
+    def fk64(self, q9, body):
+        p, R = np.zeros((len(q9), 3)), np.zeros((len(q9), 9))
+        for i in range(len(q9)):
+            self.lib.pmge_probe_fk64(_fp(q9[i]), int(body[i]), _fp(p[i]), _fp(R[i]))
+        return p, R
+
+    def cyl_redo64(self, blks, kc):
+        n, out = np.zeros(len(blks), np.int32), np.zeros((len(blks), 40), np.float32)
+        q9, door = np.zeros(9, np.float32), np.zeros(4, np.float32)
+        for i in range(len(blks)):
+            n[i] = self.lib.pmge_probe_cyl_redo64(-1, 0, -1, -1, _fp(q9), _fp(blks[i]), _fp(door), _fp(kc), C.c_float(0.03), C.c_float(0.01), _fp(out[i]))
+        return n, out
 
 
-def test_device_ik_matches_oracle(emu_library):
-    lib = C.CDLL(emu_library.path)
-    q0 = np.float32([0, -0.5592432, 0, 1.733180, 0, -0.8501557, 0, 0.035, 0.035])
-    for tgt in ([-0.52, 0.0, 0.25], [-0.45, 0.1, 0.30]):
-        out = np.zeros(9, np.float32)
-        lib.pmge_probe_ik(_fp(q0), _fp(np.float32(tgt)), _fp(out))
-        ref, it = O.ik(q0.astype(float), tgt)
-        assert np.abs(out - ref).max() < 5e-5
+@pytest.fixture(scope='module')
+def emu_run(emu_library):
+    return EmuRunners(emu_library)
+
+
+def test_device_dynamics_functions_match_oracle(emu_run):
+    D.check_dynamics(D.dynamics_cases_basic(), emu_run.dynamics)
+
+
+def test_device_ik_matches_oracle(emu_run):
+    D.check_ik(D.ik_cases_basic(), emu_run.ik)
 
 
 @pytest.mark.parametrize('task,kw,steps,tol', [
@@ -408,164 +448,47 @@ def test_emulated_row_packed_object_tasks_and_overflow_redo(emu_library):
 
 
 @pytest.mark.parametrize('kind', ['box', 'cyl'])
-def test_device_narrowphase_matches_oracle_on_random_pairs(emu_library, kind):
+def test_device_narrowphase_matches_oracle_on_random_pairs(emu_run, kind):
     """The HIP narrowphase functions (box_box_fast -> box_box, cyl_box), called directly in the emulator build, against
     the oracle's on randomly oriented pairs in the regime the simulation lives in (brought together until first touch,
     then a little deeper): same number of points, normals, depths and witness points."""
-    lib = C.CDLL(emu_library.path)
-    lib.pmge_probe_narrowphase.restype = C.c_int
-    rs = np.random.RandomState(4)
-
-    def rot():
-        q = rs.normal(size=4); q /= np.linalg.norm(q); x, y, z, w = q
-        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-    hb = np.float32([0.015, 0.015, 0.015])
-    ha = np.float32([0.0125, 0.005, 0.04]) if kind == 'box' else np.float32([0.03, 0.03, 0.01])
-    checked = tilted = loose = general_loose = 0
-    for trial in range(100):
-        Ra, Rb = (np.eye(3), np.eye(3)) if trial % 4 == 0 else (rot(), rot())
-        if trial % 4 == 1:
-            # bodies tilted by <= 3 degrees out of the table plane, any yaw: rim x edge crossings, the extrapolated closest
-            # pair and the edge refinement of cyl_box (round 4) are taken here
-            from test_oracle_physics import _rot_axis
-            Ra = _rot_axis(rs.normal(size=3), rs.uniform(0, 0.05))
-            Rb = _rot_axis(rs.normal(size=3), rs.uniform(0, 0.05)) @ _rot_axis(np.array([0.0, 0.0, 1.0]), rs.uniform(0, 2 * np.pi))
-        cb = rs.uniform(-0.1, 0.1, 3)
-        u = rs.normal(size=3); u /= np.linalg.norm(u)
-        for step in range(0, 200):
-            ca = cb + u * (0.09 - 0.0005 * step)
-            ref = (O.box_box(ca, Ra.ravel(), ha, cb, Rb.ravel(), hb) if kind == 'box'
-                   else O.cyl_box(ca, Ra.ravel(), 0.03, 0.01, cb, Rb.ravel(), hb))
-            if len(ref):
-                break
-        for extra in (0.0, 0.0007):                       # at first touch and slightly deeper
-            ca2 = np.float32(ca - u * extra)
-            a32 = [np.float32(x) for x in (ca2, Ra.ravel(), ha, cb, Rb.ravel(), hb)]
-            ref = (O.box_box(*[x.astype(float) for x in a32]) if kind == 'box'
-                   else O.cyl_box(a32[0].astype(float), a32[1].astype(float), 0.03, 0.01, a32[3].astype(float), a32[4].astype(float), hb))
-            out = np.zeros(40, np.float32)
-            n = lib.pmge_probe_narrowphase(0 if kind == 'box' else 1, *[_fp(x) for x in a32], C.c_float(0.002), _fp(out))
-            got = out.reshape(4, 10)[:n]
-            if n != len(ref):
-                # a point sitting exactly on the margin / a tie between axes may flip between float32 and float64
-                assert abs(n - len(ref)) <= 1 and (len(ref) == 0 or np.abs(ref[:, 9]).max() < 0.0021)
-                continue
-            if n == 0:
-                continue
-            checked += 1
-            order_g, order_r = np.lexsort(got[:, :3].round(4).T), np.lexsort(ref[:, :3].round(4).T)
-            en = np.abs(got[order_g][:, 6:9] - ref[order_r][:, 6:9]).max()
-            ed = np.abs(got[order_g][:, 9] - ref[order_r][:, 9]).max()
-            ep = np.abs(got[order_g][:, 0:6] - ref[order_r][:, 0:6]).max()
-            if trial % 4 == 1:
-                # two almost parallel features: the closest pair's position along them, and with it the last third of a degree
-                # of the normal, is ill-conditioned -- float32 and float64 settle on different points of a flat minimum.
-                # The depth is not: strict bar on it, loose bars on the rest, and a count of the strict misses
-                tilted += 1
-                assert ed < 1e-4 and en < 2e-2 and ep < 1e-2, (en, ed, ep)
-                loose += int(en >= 2e-4 or ed >= 2e-5 or ep >= 5e-5)
-                continue
-            if not (en < 2e-4 and ed < 2e-5 and ep < 5e-5):
-                # (cyl, any orientation) the closest-feature direction of two features that are nearly parallel by chance
-                general_loose += 1
-                assert kind == 'cyl' and ed < 1e-4 and en < 2e-2 and ep < 1e-2, (en, ed, ep)
-    print('tilted pairs %d, beyond the strict bars %d; other pairs %d, beyond the strict bars %d' % (tilted, loose, checked - tilted, general_loose))
-    assert loose <= 0.25 * max(tilted, 1) and general_loose <= 0.03 * checked
-    assert checked > 130
+    D.check_random_pairs(kind, emu_run.narrowphase)
 
 
-def test_device_cyl_box_corner_in_the_side_matches_oracle(emu_library):
+def test_device_cyl_box_corner_in_the_side_matches_oracle(emu_run):
     """The product's cyl_box on a box corner touching / inside the cylinder's side (a finger's edge against the puck): the
     planar corner-to-circle distance, as the oracle -- in float32 the coinciding closest points of penetrating shapes are
     1e-8 apart, not 0, so the switch to the radial axis sits at 1 um in both."""
-    lib = C.CDLL(emu_library.path)
-    lib.pmge_probe_narrowphase.restype = C.c_int
-    I = np.eye(3, dtype=np.float32).ravel()
-    cc, ha, hb = np.float32([-0.495, 0.0979, 0.17]), np.float32([0.03, 0.03, 0.01]), np.float32([0.0125, 0.005, 0.04])
-    checked = 0
-    for yoff in (0.0157, 0.0257):
-        for gap in np.arange(0.042, 0.028, -0.001):
-            cb = np.float32([cc[0] + gap, cc[1] + yoff, 0.207])
-            out = np.zeros(40, np.float32)
-            n = lib.pmge_probe_narrowphase(1, _fp(cc), _fp(I), _fp(ha), _fp(cb), _fp(I), _fp(hb), C.c_float(0.002), _fp(out))
-            ref = O.cyl_box(cc.astype(float), I.astype(float), 0.03, 0.01, cb.astype(float), I.astype(float), hb.astype(float))
-            assert n == len(ref), (yoff, gap, n, len(ref))
-            if n:
-                got = out.reshape(4, 10)[:n]
-                assert abs(got[:, 9].min() - ref[:, 9].min()) < 2e-6 and np.abs(got[0, 6:9] - ref[0, 6:9]).max() < 1e-4, (yoff, gap, got[:, 9], ref[:, 9])
-                checked += 1
-    assert checked > 10
+    D.check_corner_in_side(emu_run.narrowphase)
 
 
-def test_axis_aligned_partner_front_end_is_bit_identical(emu_library):
+def test_device_box_box_on_cubes_stacked_flush_matches_oracle(emu_run):
+    """vertices of the incident face exactly ON the clip planes of the reference face (cubes stacked off-centre with flush
+    sides, a cube in the table's corner): four points, the oracle's, from box_box_fast and from the general box_box"""
+    assert D.check_flush_stacks(emu_run.narrowphase, D.NP_FAST) > 40
+    D.check_flush_stacks(emu_run.narrowphase, D.NP_GENERAL)
+
+
+def test_axis_aligned_partner_front_end_is_bit_identical(emu_run):
     """The reach kernel's narrowphase instantiation knows that box B (the table) is axis-aligned and leaves the sums with
     exact zeros out of the separating-axis front end: same contacts, same bits as the general routine on fingers in
     random poses over, in and beside a table-sized box."""
-    lib = C.CDLL(emu_library.path)
-    lib.pmge_probe_narrowphase.restype = C.c_int
-    rs = np.random.RandomState(3)
-    ha, hb = np.float32([0.0125, 0.005, 0.04]), np.float32([0.5, 0.4, 0.1])
-    Rb = np.eye(3, dtype=np.float32)
-    hit = 0
-    for trial in range(600):
-        q = rs.normal(size=4) * ([1, 1, 1, 1] if trial % 3 == 0 else [0.02, 0.02, 1, 1]); q /= np.linalg.norm(q); x, y, z, w = q
-        Ra = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                       [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                       [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-        ext = np.abs(Ra[2]) @ ha                                     # the finger's half extent along z
-        cb = np.float32([0, 0, 0])
-        ca = np.float32([rs.uniform(-0.52, 0.52), rs.uniform(-0.42, 0.42), 0.1 + ext + rs.uniform(-0.002, 0.003)])
-        a32 = [np.float32(v) for v in (ca, Ra.ravel(), ha, cb, Rb.ravel(), hb)]
-        o1, o2 = np.zeros(40, np.float32), np.zeros(40, np.float32)
-        n1 = lib.pmge_probe_narrowphase(3, *[_fp(v) for v in a32], C.c_float(0.002), _fp(o1))
-        n2 = lib.pmge_probe_narrowphase(2, *[_fp(v) for v in a32], C.c_float(0.002), _fp(o2))
-        assert n1 == n2, (trial, n1, n2)
-        assert np.array_equal(o1[:10 * n1].view(np.uint32), o2[:10 * n2].view(np.uint32)), trial
-        hit += n1 > 0
+    n = D.check_two_routines_bit_identical(D.axis_aligned_cases(), emu_run.narrowphase, D.NP_FAST_ALIGNED, D.NP_GENERAL)
+    hit = int((n > 0).sum())
     assert hit > 250, hit
 
 
-def test_face_clip_is_bit_identical_to_the_general_box_box_routine(emu_library):
+def test_face_clip_is_bit_identical_to_the_general_box_box_routine(emu_run):
     """box_box_fast serves a face contact whose incident face is NOT inside the reference face (a finger on a cube, cubes
     stacked off-centre) with box_face_clip: clip passes over all vertices at once, batched LDS traffic.  It must return
     exactly what the general routine (box_box: vertex-by-vertex Sutherland-Hodgman through the workspace) returns -- same
     points, same order, same bits -- on fingers against cubes, cubes on cubes and cubes on a table-sized box, in random
     orientations, touching, deeper and with more than four clipped vertices inside the margin."""
-    lib = C.CDLL(emu_library.path)
-    lib.pmge_probe_narrowphase.restype = C.c_int
-    rs = np.random.RandomState(11)
-
-    def rot(small):
-        q = rs.normal(size=4) * ([small, small, 1.0, 1.0] if small else 1.0); q /= np.linalg.norm(q); x, y, z, w = q
-        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-    shapes = [(np.float32([0.0125, 0.005, 0.04]), np.float32([0.015] * 3)),      # finger x cube
-              (np.float32([0.015] * 3), np.float32([0.015] * 3)),                # cube x cube
-              (np.float32([0.015] * 3), np.float32([0.5, 0.5, 0.1]))]            # cube x table-sized box
+    lib = emu_run.lib
     lib.pmge_face_clip_count.restype = C.c_longlong
     calls0 = lib.pmge_face_clip_count()
-    clipped = many = 0
-    for trial in range(900):
-        ha, hb = shapes[trial % 3]
-        small = 0.0 if trial % 2 else rs.choice([0.003, 0.03, 0.3])               # nearly face-parallel poses clip most
-        Ra, Rb = rot(small), (np.eye(3) if trial % 5 else rot(small))
-        n_ax = Rb[:, rs.randint(3)] * rs.choice([-1, 1])
-        reach = np.abs(Ra.T @ n_ax) @ ha + np.abs(Rb.T @ n_ax) @ hb
-        lateral = rs.normal(size=3); lateral -= n_ax * (lateral @ n_ax)
-        lateral *= rs.uniform(0, 1) * float(min(hb.min(), 0.03)) / max(np.linalg.norm(lateral), 1e-9)
-        cb = rs.uniform(-0.1, 0.1, 3)
-        ca = cb + n_ax * (reach - rs.uniform(-0.001, 0.003)) + lateral
-        a32 = [np.float32(x) for x in (ca, Ra.ravel(), ha, cb, Rb.ravel(), hb)]
-        o_new, o_old = np.zeros(40, np.float32), np.zeros(40, np.float32)
-        n_new = lib.pmge_probe_narrowphase(0, *[_fp(x) for x in a32], C.c_float(0.002), _fp(o_new))
-        n_old = lib.pmge_probe_narrowphase(2, *[_fp(x) for x in a32], C.c_float(0.002), _fp(o_old))
-        assert n_new == n_old, (trial, n_new, n_old)
-        assert np.array_equal(o_new[:10 * n_new].view(np.uint32), o_old[:10 * n_old].view(np.uint32)), (trial, o_new[:10 * n_new], o_old[:10 * n_old])
-        clipped += n_new > 0
-        many += n_new == 4
+    n = D.check_two_routines_bit_identical(D.face_clip_cases(), emu_run.narrowphase, D.NP_FAST, D.NP_GENERAL)
+    clipped, many = int((n > 0).sum()), int((n == 4).sum())
     assert clipped > 300 and many > 100, (clipped, many)
     assert lib.pmge_face_clip_count() - calls0 > 250          # the new path is what answered
 
@@ -617,78 +540,15 @@ def test_emulated_sharded_batch_is_bit_identical_to_the_unsharded_batch(emu_libr
     _sharded_equals_unsharded(emu_library, task, 24, 3, 4)
 
 
-def _quat_R64(q):
-    x, y, z, w = [float(v) for v in q]
-    s = 2.0 / (x * x + y * y + z * z + w * w)
-    xs, ys, zs = x * s, y * s, z * s
-    wx, wy, wz, xx, xy, xz, yy, yz, zz = w * xs, w * ys, w * zs, x * xs, x * ys, x * zs, y * ys, y * zs, z * zs
-    return np.array([[1 - (yy + zz), xy - wz, xz + wy], [xy + wz, 1 - (xx + zz), yz - wx], [xz - wy, yz + wx, 1 - (xx + yy)]])
-
-
-def test_double_forward_kinematics_of_the_contact_links_matches_the_oracle(emu_library):
+def test_double_forward_kinematics_of_the_contact_links_matches_the_oracle(emu_run):
     """fk64_link (the double poses cyl_redo64 takes for the gripper base and the fingers, from float32 joint angles) against
     the float64 oracle's kinematics() through its Bullet-call-level world: link frames of Bullet links 12 / 13 / 15."""
-    lib = C.CDLL(emu_library.path)
-    ora = O.OracleEnv('reach', 1, seed_base=0)
-    ora.reset()
-    ol = ora.lib
-    rs = np.random.RandomState(3)
-    for trial in range(20):
-        q = np.float32(np.concatenate([rs.uniform(-2, 2, 7), rs.uniform(0, 0.035, 2)]))
-        for d in range(9):
-            ol.pmgo_bw_reset_joint(ora.h, 0, d, C.c_double(float(q[d])), C.c_double(0.0))
-        for body, link in ((7, 12), (5, 13), (6, 15)):                 # BODY_GBASE, BODY_FINGER1, BODY_FINGER2
-            p, R, ref = np.zeros(3), np.zeros(9), np.zeros(13)
-            lib.pmge_probe_fk64(_fp(q), body, _fp(p), _fp(R))
-            ol.pmgo_bw_link_state(ora.h, link, _fp(ref))
-            assert np.abs(p - ref[:3]).max() < 1e-12, (trial, body, p, ref[:3])
-            assert np.abs(R.reshape(3, 3) - _quat_R64(ref[3:7])).max() < 1e-12
-    ora.close()
+    D.check_fk64(emu_run.fk64)
 
 
-def test_double_repeat_of_a_cylinder_pair_is_the_float64_oracle(emu_library):
+def test_double_repeat_of_a_cylinder_pair_is_the_float64_oracle(emu_run):
     """cyl_redo64 (cyl_box<double> on poses re-derived in double from the float32 state) against the float64 oracle's cyl_box on
     the same poses: the slide puck -- any small tilt, any yaw -- against the table and near its edge.  Same count, points and
     normals to 1e-6 (the outputs are float32), depths to 1e-8.  Beside it the float32 pass on float32 poses: its gross
     disagreements with the oracle are counted (the resting puck has none: the repeat is for vertex / edge contacts)."""
-    lib = C.CDLL(emu_library.path)
-    lib.pmge_probe_cyl_redo64.restype = C.c_int
-    lib.pmge_probe_cyl_amb.restype = C.c_int
-    rs = np.random.RandomState(5)
-    I3 = np.eye(3)
-    checked = flagged = gross_unflagged = 0
-    q9 = np.zeros(9, np.float32)
-    door = np.zeros(4, np.float32)
-    for trial in range(300):
-        tilt = 10.0 ** rs.uniform(-8, -1.5) * rs.normal(size=2)
-        yaw = rs.uniform(0, 2 * np.pi)
-        quat = np.array([tilt[0] / 2, tilt[1] / 2, np.sin(yaw / 2), np.cos(yaw / 2)])
-        quat /= np.linalg.norm(quat)
-        edge = trial % 3 == 0
-        blk = np.zeros(13, np.float32)
-        blk[0:3] = [-0.70 + (0.5 - rs.uniform(0, 0.04) if edge else rs.uniform(-0.3, 0.3)), rs.uniform(-0.3, 0.3), 0.16 + 0.01 + rs.uniform(-2e-4, 1.5e-3)]
-        blk[3:7] = quat
-        tc, th = np.float32([-0.70, 0.0, 0.08]), np.float32([0.5, 0.45, 0.08])
-        out = np.zeros(40, np.float32)
-        kc = np.zeros(24, np.float32); kc[0:3] = tc; kc[3:6] = th
-        n = lib.pmge_probe_cyl_redo64(-1, 0, -1, -1, _fp(q9), _fp(blk), _fp(door), _fp(kc), C.c_float(0.03), C.c_float(0.01), _fp(out))
-        R = _quat_R64(blk[3:7])
-        ref = O.cyl_box(blk[0:3].astype(float), R.ravel(), 0.03, 0.01, tc.astype(float), I3.ravel(), th.astype(float))
-        assert n == len(ref), (trial, n, len(ref))
-        if n == 0:
-            continue
-        got = out.reshape(4, 10)[:n]
-        assert np.abs(got[:, 6:9] - ref[:, 6:9]).max() < 1e-6 and np.abs(got[:, 9] - ref[:, 9]).max() < 1e-8 and np.abs(got[:, 0:6] - ref[:, 0:6]).max() < 1e-6, (trial, got, ref)
-        checked += 1
-        Rf = np.float32(R)                                     # the float pass: float32 poses
-        outf, amb = np.zeros(40, np.float32), C.c_float(0)
-        nf = lib.pmge_probe_cyl_amb(_fp(blk), _fp(Rf), C.c_float(0.03), C.c_float(0.01), _fp(tc), _fp(np.float32(I3)), _fp(th), C.c_float(0.002), _fp(outf), C.byref(amb))
-        gf = outf.reshape(4, 10)[:nf]
-        # gross: another number of points, another normal, a point 3 mm from the oracle's or 20 um deeper (two candidates of the
-        # same depth 1 mm apart on the rim may swap in the reduction to four points: not a different contact)
-        gross = nf != n or np.abs(np.sort(gf[:, 0:3], axis=0) - np.sort(ref[:, 0:3], axis=0)).max() > 3e-3 or np.abs(gf[0, 6:9] - ref[0, 6:9]).max() > 1e-2 \
-            or np.abs(np.sort(gf[:, 9]) - np.sort(ref[:, 9])).max() > 2e-5
-        flagged += int(amb.value < 1.0)
-        gross_unflagged += int(gross and not amb.value < 1.0)
-    print('cylinder pairs in contact %d, float pass flagged ambiguous %d, gross float32 answers not flagged %d' % (checked, flagged, gross_unflagged))
-    assert checked > 150 and gross_unflagged <= 0.02 * checked and flagged < 0.2 * checked
+    D.check_cyl_redo64(emu_run.cyl_redo64, emu_run.narrowphase_amb)
