@@ -202,13 +202,67 @@ __global__ void __launch_bounds__(64) k_cyl_redo64(int n, int ck, const float* q
     if (l < n) {
         for (int a = 0; a < 4 * pmg::CP; a++) out[l][a] = 0.f;
         int m;
-        /* the slide puck (free body 0) against the table: the pair the emulated test drives */
+        /* the slide puck (free body 0) against the table alone; every other pair: k_cyl_redo64_pairs */
         if (ck == 0) m = pmg::cyl_redo64<0>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
         else if (ck == 1) m = pmg::cyl_redo64<1>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
         else m = pmg::cyl_redo64<-1>(0, pmg::BODY_STATIC, -1, q9 + 9 * l, blk + pmg::BLOCK_DIM * l, doorq + l, kc, prad, phl, out[l], W[l]);
         m = m < 0 ? 0 : (m > 4 ? 4 : m);
         for (int a = 0; a < 4 * pmg::CP; a++) outp[4 * pmg::CP * l + a] = out[l][a];
         nout[l] = m;
+    }
+}
+
+/* cyl_redo64 on ANY of the pairs collide() hands it: one case per lane, the lanes of a launch carrying different kinds of pair,
+ * so that the out-of-line callee is entered divergently as in collide().  ids: cyl_body, box_body, wall, handed per case (checked
+ * by the host entry); blk: TWO free-body rows per case.  handed: the lane first derives its robot body's double pose the way
+ * spec_fk does -- sincos64 per arm joint into a table in LDS, fk64_chain with that table -- and hands it in (spec_pairs) */
+constexpr int REDO_IDS = 4, REDO_ROWS = 2;
+__device__ __forceinline__ int redo_robot_body(int cyl_body, int box_body)
+{
+    if (cyl_body == pmg::BODY_GBASE) return pmg::BODY_GBASE;
+    return (box_body == pmg::BODY_FINGER1 || box_body == pmg::BODY_FINGER2) ? box_body : -1;
+}
+template <int CK>
+__device__ __forceinline__ int redo_pair(const int* id, const float* q9, const float* blk, const float* doorq, const float* kc, float prad, float phl, float* out, float* W,
+                                         double (*sc)[2])
+{
+    const int rb = redo_robot_body(id[0], id[1]);
+    if (id[3] && rb >= 0) {
+        double p[3], R[9];
+        for (int j = 0; j < 7; j++) pmg::sincos64((double)q9[j], sc[j][0], sc[j][1]);
+        pmg::fk64_chain(q9, sc, rb, p, R);
+        return pmg::cyl_redo64<CK>(id[0], id[1], id[2], q9, blk, doorq, kc, prad, phl, out, W, p, R);
+    }
+    return pmg::cyl_redo64<CK>(id[0], id[1], id[2], q9, blk, doorq, kc, prad, phl, out, W);
+}
+__global__ void __launch_bounds__(64) k_cyl_redo64_pairs(int n, int ck, const int* ids, const float* q9, const float* blk, const float* doorq, const float* kc, float prad,
+                                                         float phl, float* outp, int* nout)
+{
+    __shared__ __attribute__((aligned(16))) float out[64][4 * pmg::CP], W[64][pmg::BOX_WORK];
+    __shared__ double sc[64][7][2];
+    const int l = (int)threadIdx.x & 63;
+    n = n < 64 ? n : 64;
+    if (l < n) {
+        for (int a = 0; a < 4 * pmg::CP; a++) out[l][a] = 0.f;
+        const int* id = ids + REDO_IDS * l;
+        const float *q = q9 + 9 * l, *b = blk + REDO_ROWS * pmg::BLOCK_DIM * l;
+        int m;
+        if (ck == 0) m = redo_pair<0>(id, q, b, doorq + l, kc, prad, phl, out[l], W[l], sc[l]);
+        else if (ck == 1) m = redo_pair<1>(id, q, b, doorq + l, kc, prad, phl, out[l], W[l], sc[l]);
+        else m = redo_pair<-1>(id, q, b, doorq + l, kc, prad, phl, out[l], W[l], sc[l]);
+        m = m < 0 ? 0 : (m > 4 ? 4 : m);
+        for (int a = 0; a < 4 * pmg::CP; a++) outp[4 * pmg::CP * l + a] = out[l][a];
+        nout[l] = m;
+    }
+}
+/* the double arithmetic of the repeat, one element per lane.  op 0: t_sqrt(x) -> o0; 1: t_div(x, y) -> o0; 2: sincos64(x) -> o0, o1 */
+__global__ void __launch_bounds__(64) k_double_maths(int op, int n, const double* x, const double* y, double* o0, double* o1)
+{
+    const int l = (int)threadIdx.x & 63;
+    for (int i = l; i < n; i += 64) {
+        if (op == 0) o0[i] = pmg::t_sqrt(x[i]);
+        else if (op == 1) o0[i] = pmg::t_div(x[i], y[i]);
+        else pmg::sincos64(x[i], o0[i], o1[i]);
     }
 }
 
@@ -308,8 +362,8 @@ int pmgd_fk64(int n, const float* q9, const int* body, double* p, double* R)
     d.down(p, dp, 3 * (size_t)n); d.down(R, dR, 9 * (size_t)n);
     return (int)d.err;
 }
-/* cyl_redo64<ck> of the puck (free body 0 of each case's state row) against the table: q9 [n][9], blk [n][13], doorq [n],
- * kc [24] -> out [n][40], nout [n] */
+/* cyl_redo64<ck> of the puck (free body 0 of each case's state row) against the table only: q9 [n][9], blk [n][13], doorq [n],
+ * kc [24] -> out [n][40], nout [n].  Every other pair the routine serves goes through pmgd_cyl_redo64_pairs below */
 int pmgd_cyl_redo64(int n, int ck, const float* q9, const float* blk, const float* doorq, const float* kc, float prad, float phl, float* out, int* nout)
 {
     if (n < 1 || n > 65536 || ck < -1 || ck > 1) return -1;
@@ -324,6 +378,52 @@ int pmgd_cyl_redo64(int n, int ck, const float* q9, const float* blk, const floa
     }
     d.sync();
     d.down(out, dout, 40 * (size_t)n); d.down(nout, dn, (size_t)n);
+    return (int)d.err;
+}
+
+/* cyl_redo64<ck> on any of its pairs, `lanes` (1..64) cases per launch, one per lane.  ids [n][4]: cyl_body (a free-body row 0 / 1,
+ * BODY_GBASE or CYL64_HANDLE), box_body (a row 0 / 1, BODY_FINGER1 / 2, BODY_DOOR or BODY_STATIC), wall (-1: table / floor), handed
+ * (0 / 1: the robot body's pose handed in as spec_pairs does); q9 [n][9], blk [n][2][13], doorq [n], kc [24] -> out [n][40], nout [n].
+ * Ids the routine would index out of these arrays with (the handle, the door or a wall without a chest, a row beyond the second, a
+ * wall the chest kind does not have) are refused here */
+int pmgd_cyl_redo64_pairs(int n, int ck, int lanes, const int* ids, const float* q9, const float* blk, const float* doorq, const float* kc, float prad, float phl,
+                          float* out, int* nout)
+{
+    if (n < 1 || n > 65536 || ck < -1 || ck > 1 || lanes < 1 || lanes > 64) return -1;
+    for (int i = 0; i < n; i++) {
+        const int cyl = ids[REDO_IDS * i], box = ids[REDO_IDS * i + 1], wall = ids[REDO_IDS * i + 2], handed = ids[REDO_IDS * i + 3];
+        const bool row_c = cyl >= 0 && cyl < REDO_ROWS, row_b = box >= 0 && box < REDO_ROWS;
+        if (!(row_c || cyl == pmg::BODY_GBASE || (cyl == pmg::CYL64_HANDLE && ck >= 0))) return -1;
+        if (!(row_b || box == pmg::BODY_FINGER1 || box == pmg::BODY_FINGER2 || box == pmg::BODY_STATIC || (box == pmg::BODY_DOOR && ck >= 0))) return -1;
+        if ((row_c && row_b && cyl == box) || (cyl == pmg::BODY_GBASE && (box == pmg::BODY_FINGER1 || box == pmg::BODY_FINGER2))) return -1;
+        if (wall < -1 || wall >= (ck >= 0 ? pmg::ChestT::nwall(ck) : 0) || (wall >= 0 && box != pmg::BODY_STATIC)) return -1;
+        if (handed != 0 && handed != 1) return -1;
+    }
+    Dev d;
+    const int* di = d.up(ids, REDO_IDS * (size_t)n);
+    const float *dq = d.up(q9, 9 * (size_t)n), *db = d.up(blk, REDO_ROWS * 13 * (size_t)n), *dd = d.up(doorq, (size_t)n), *dk = d.up(kc, 24);
+    float* dout = d.up<float>(nullptr, 40 * (size_t)n);
+    int* dn = d.up<int>(nullptr, (size_t)n);
+    for (int i = 0; i < n && d.err == hipSuccess; i += lanes) {
+        const int np = n - i < lanes ? n - i : lanes;
+        hipLaunchKernelGGL(k_cyl_redo64_pairs, dim3(1), dim3(64), 0, 0, np, ck, di + REDO_IDS * (size_t)i, dq + 9 * (size_t)i, db + REDO_ROWS * 13 * (size_t)i, dd + i, dk,
+                           prad, phl, dout + 40 * (size_t)i, dn + i);
+        d.err = hipGetLastError();
+    }
+    d.sync();
+    d.down(out, dout, 40 * (size_t)n); d.down(nout, dn, (size_t)n);
+    return (int)d.err;
+}
+/* t_sqrt (op 0: x -> o0), t_div (1: x / y -> o0) and sincos64 (2: x -> sin o0, cos o1) in double on arrays of n */
+int pmgd_double_maths(int op, int n, const double* x, const double* y, double* o0, double* o1)
+{
+    if (op < 0 || op > 2 || n < 1 || n > (1 << 20)) return -1;
+    Dev d;
+    const double *dx = d.up(x, (size_t)n), *dy = d.up(y, (size_t)n);
+    double *d0 = d.up<double>(nullptr, (size_t)n), *d1 = d.up<double>(nullptr, (size_t)n);
+    if (d.err == hipSuccess) hipLaunchKernelGGL(k_double_maths, dim3(1), dim3(64), 0, 0, op, n, dx, dy, d0, d1);
+    d.sync();
+    d.down(o0, d0, (size_t)n); d.down(o1, d1, (size_t)n);
     return (int)d.err;
 }
 

@@ -9,8 +9,15 @@ Runners:
     ik(q [n][9], target [n][3])      -> q_out [n][9]
     narrowphase(kind, pairs [n][30]) -> n [n], out [n][40], amb [n]      (kind: NP_* below; a pair: ca3 Ra9 ha3 cb3 Rb9 hb3)
     fk64(q9 [n][9], body [n])        -> p [n][3], R [n][9]  (float64)
-    cyl_redo64(blk [n][13], kc [24]) -> n [n], out [n][40]   (the puck, free body 0, against the table)"""
+    cyl_redo64(blk [n][13], kc [24]) -> n [n], out [n][40]   (the puck, free body 0, against the table)
+    redo_pairs(ck, ids [n][4], q9 [n][9], blk [n][2][13], doorq [n], kc [24], lanes=None) -> n [n], out [n][40]
+        (cyl_redo64<ck> on any of its pairs; an id row: cyl_body, box_body, wall, handed -- REDO_* below)
+    double_maths(op, x [n], y [n])   -> o0 [n], o1 [n]  (float64; op: DM_SQRT t_sqrt(x), DM_DIV t_div(x, y), DM_SINCOS sincos64(x))"""
 import ctypes as C
+import functools
+import itertools
+import json
+import os
 
 import numpy as np
 
@@ -409,17 +416,40 @@ def quat_R64(q):
 FK64_BODIES = ((7, 12), (5, 13), (6, 15))                 # (contact body, Bullet link): BODY_GBASE, BODY_FINGER1, BODY_FINGER2
 
 
+def fk64_edge_poses():
+    """where sincos64 changes its path: all joints at JLO, at JHI, alternating; each arm joint alone at either limit (the
+    quadrant becomes +-2 there) and, where inside its range, at the quadrant switch points +-pi/4 and +-3 pi/4, at +-pi/2, 0,
+    1e-8 and -1e-30; every one of these also one float32 step above and below (clipped to nothing: the routine takes any
+    float32 angle of |q| <= 3.06).  -> [float32 q9]"""
+    alt = np.where(np.arange(9) % 2 == 0, JLO, JHI)
+    out = [np.float32(q) for q in (JLO, JHI, alt, JLO + JHI - alt)]
+    for j in range(7):
+        for v in (JLO[j], JHI[j], np.pi / 4, -np.pi / 4, 3 * np.pi / 4, -3 * np.pi / 4, np.pi / 2, -np.pi / 2, 0.0, 1e-8, -1e-30):
+            if not JLO[j] <= v <= JHI[j]:
+                continue
+            v32 = np.float32(v)
+            for w in (v32, np.nextafter(v32, np.float32(4)), np.nextafter(v32, np.float32(-4))):
+                q = Q_START.copy()
+                q[j] = w
+                out.append(q)
+    return out
+
+
 def check_fk64(run):
     """fk64_link against the float64 oracle's kinematics() through its Bullet-call-level world: link frames of Bullet links
-    12 / 13 / 15 at 20 random poses"""
+    12 / 13 / 15 at 20 random poses and at the edge poses of fk64_edge_poses(), to 1e-12.  -> the largest error"""
     ora = O.OracleEnv('reach', 1, seed_base=0)
     ora.reset()
     ol = ora.lib
     rs = np.random.RandomState(3)
     qs = [np.float32(np.concatenate([rs.uniform(-2, 2, 7), rs.uniform(0, 0.035, 2)])) for _ in range(20)]
+    edges = fk64_edge_poses()
+    assert len(edges) >= 4 + 3 * 7 * 6
+    qs += edges
     q9 = np.ascontiguousarray(np.repeat(np.stack(qs), 3, axis=0), np.float32)
-    body = np.ascontiguousarray(np.tile([b for b, _ in FK64_BODIES], 20), np.int32)
+    body = np.ascontiguousarray(np.tile([b for b, _ in FK64_BODIES], len(qs)), np.int32)
     p, R = run(q9, body)
+    worst = 0.0
     for trial, q in enumerate(qs):
         for d in range(9):
             ol.pmgo_bw_reset_joint(ora.h, 0, d, C.c_double(float(q[d])), C.c_double(0.0))
@@ -427,9 +457,12 @@ def check_fk64(run):
             ref = np.zeros(13)
             ol.pmgo_bw_link_state(ora.h, link, _fp(ref))
             i = 3 * trial + k
-            assert np.abs(p[i] - ref[:3]).max() < 1e-12, (trial, b, p[i], ref[:3])
-            assert np.abs(R[i].reshape(3, 3) - quat_R64(ref[3:7])).max() < 1e-12
+            ep, eR = np.abs(p[i] - ref[:3]).max(), np.abs(R[i].reshape(3, 3) - quat_R64(ref[3:7])).max()
+            assert ep < 1e-12 and eR < 1e-12, (trial, b, q, ep, eR)
+            worst = max(worst, ep, eR)
     ora.close()
+    print('fk64_link: %d poses, largest error %.3g' % (len(qs), worst))
+    return worst
 
 
 def cyl_redo64_cases():
@@ -482,3 +515,555 @@ def check_cyl_redo64(run_redo, run_pairs):
         gross_unflagged += int(gross and not amb < 1.0)
     print('cylinder pairs in contact %d, float pass flagged ambiguous %d, gross float32 answers not flagged %d' % (checked, flagged, gross_unflagged))
     assert checked > 150 and gross_unflagged <= 0.02 * checked and flagged < 0.2 * checked
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# cyl_redo64 on EVERY pair collide() hands it.  Every reference value below comes from the float64 oracle and from
+# tests/golden/model.json; nothing from include/pmg_model.h, nothing from the device
+REDO_STATIC, REDO_FINGER1, REDO_FINGER2, REDO_GBASE, REDO_DOOR, REDO_HANDLE = -1, 5, 6, 7, 8, 100      # the ids of the call
+DM_SQRT, DM_DIV, DM_SINCOS = 0, 1, 2
+MODEL = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'model.json')))
+FINGER_H = np.array(MODEL['finger_half'])
+CUBE_H = np.array(MODEL['block']['ext']) / 2
+PUCK_R, PUCK_HL = MODEL['puck']['ext'][0] / 2, MODEL['puck']['ext'][2] / 2
+GBASE_R, GBASE_HL = MODEL['gbase_radius'], MODEL['gbase_halflen']
+PLANE_H = np.array(MODEL['plane']['ext']) / 2
+SLIDE_TABLE_C, SLIDE_TABLE_H = np.array([-0.70, 0.0, 0.08]), np.array(MODEL['long_table']['ext']) / 2
+PLANE_SWITCH_Z = 0.04                  # (oracle/pmg_oracle.c) a free body below it meets the floor, above it the table
+REDO_BARS = (1e-6, 1e-8, 1e-6)         # normal, depth, points: the bars of check_cyl_redo64
+_LINK = {REDO_GBASE: 12, REDO_FINGER1: 13, REDO_FINGER2: 15}
+FAR_ROW = np.float32([3.0, 3.0, 3.0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0])       # the other free-body row: identity, far away
+
+
+def redo_kc():
+    """the env's constant table as far as cyl_redo64 reads it: table centre / half at 0 / 3, cube half at 18, floor half at 21"""
+    kc = np.zeros(24, np.float32)
+    kc[0:3], kc[3:6], kc[18:21], kc[21:24] = SLIDE_TABLE_C, SLIDE_TABLE_H, CUBE_H, PLANE_H
+    kc[6:15] = np.eye(3).ravel()
+    return kc
+
+
+class _Arm:
+    """double poses of the contact links from float32 joint angles: the oracle's Bullet-call-level world, as check_fk64"""
+
+    def __init__(self):
+        self.ora = O.OracleEnv('reach', 1, seed_base=0)
+        self.ora.reset()
+
+    def pose(self, q9, body):
+        ol, ref = self.ora.lib, np.zeros(13)
+        for d in range(9):
+            ol.pmgo_bw_reset_joint(self.ora.h, 0, d, C.c_double(float(np.float32(q9[d]))), C.c_double(0.0))
+        ol.pmgo_bw_link_state(self.ora.h, _LINK[body], _fp(ref))
+        return ref[:3].copy(), quat_R64(ref[3:7])
+
+
+@functools.lru_cache(None)
+def chest_base(ck):
+    """where the chest stands, from the oracle's reset observation of a chest env (the door's first key point, float32, less the
+    door's and the key point's offsets of model.json), rounded to the micrometre the layout is written in"""
+    ch = MODEL['chest'][ck]
+    ora = O.OracleEnv(('chest_push', 'chest_pick_and_place')[ck], 1, num_block=1, seed_base=5, seed_stride=1)
+    ora.reset()
+    obs = ora.reset()['observation'][0]
+    ora.close()
+    kp = obs[8 + 16:][2:].reshape(3, 6)[:, :3].astype(float)
+    base = [np.round(kp[k] - ch['door_c'] - ch['keypoints'][k], 6) for k in range(3)]
+    assert np.array_equal(base[0], base[1]) and np.array_equal(base[0], base[2]), base
+    return base[0] + 0.0
+
+
+def redo_geometry(arm, ck, cyl, box, wall, q9, blk, doorq, kc):
+    """the operands cyl_redo64 is to assemble for this call, from the oracle and model.json: -> cc, Rc, rad, hl, cb, Rb, hb"""
+    I3 = np.eye(3)
+    if ck >= 0:
+        ch = MODEL['chest'][ck]
+        dc = chest_base(ck) + np.array(ch['door_c']) + np.array(ch['axis']) * float(np.float32(doorq))
+    if cyl == REDO_GBASE:
+        (cc, Rc), rad, hl = arm.pose(q9, REDO_GBASE), GBASE_R, GBASE_HL
+    elif cyl == REDO_HANDLE:
+        cc, Rc, rad, hl = dc + np.array(ch['handle_c']), np.array(ch['handle_R']), ch['handle_radius'], ch['handle_halflen']
+    else:
+        cc, Rc, rad, hl = blk[cyl, 0:3].astype(float), quat_R64(blk[cyl, 3:7]), PUCK_R, PUCK_HL
+    if box in (REDO_FINGER1, REDO_FINGER2):
+        (cb, Rb), hb = arm.pose(q9, box), FINGER_H
+    elif box == REDO_DOOR:
+        cb, Rb, hb = dc, I3, np.array(ch['door_half'])
+    elif box == REDO_STATIC and wall >= 0:
+        w = ch['walls'][wall]
+        cb, Rb, hb = chest_base(ck) + np.array(w['c']), I3, np.array(w['half'])
+    elif box == REDO_STATIC:
+        if blk[cyl, 2] < np.float32(PLANE_SWITCH_Z):
+            cb, Rb, hb = np.zeros(3), I3, kc[21:24].astype(float)
+        else:
+            cb, Rb, hb = kc[0:3].astype(float), I3, kc[3:6].astype(float)
+    else:
+        cb, Rb, hb = blk[box, 0:3].astype(float), quat_R64(blk[box, 3:7]), kc[18:21].astype(float)
+    return cc, Rc, rad, hl, cb, Rb, hb
+
+
+def _oracle_cyl(g, margin=0.002, f32=False):
+    return O.cyl_box(g[0], np.asarray(g[1]).ravel(), g[2], g[3], g[4], np.asarray(g[5]).ravel(), g[6], margin=margin, f32=f32)
+
+
+def _unit(rs):
+    u = rs.normal(size=3)
+    return u / np.linalg.norm(u)
+
+
+def _rand_quat(rs):
+    q = rs.normal(size=4)
+    return np.float32(q / np.linalg.norm(q))
+
+
+def _support_box(R, h, u):
+    return float(np.abs(np.asarray(R).T @ u) @ h)
+
+
+def _support_cyl(R, rad, hl, u):
+    a = float(np.asarray(R)[:, 2] @ u)
+    return abs(a) * hl + rad * np.sqrt(max(0.0, 1.0 - a * a))
+
+
+def _first_touch(count_at, d0, coarse=0.002, fine=0.0003):
+    """d walked down from d0 (out of contact by a separating axis) in 0.3 mm steps until the oracle reports the first touch; the
+    first 2 mm strides only skip the empty part of the way.  -> d, or None (never touched within 25 cm / touched at the start)"""
+    d = d0
+    if count_at(d):
+        return None
+    while not count_at(d - coarse):
+        d -= coarse
+        if d < d0 - 0.25:
+            return None
+    while not count_at(d):
+        d -= fine
+    return d
+
+
+class _Cases:
+    def __init__(self, ck):
+        self.ck, self.rows, self.ids, self.q9, self.blk, self.door, self.geo, self.ref = ck, [], [], [], [], [], [], []
+        self.dropped = 0
+
+    def add(self, arm, row, cyl, box, wall, q9, blk, doorq, kc):
+        q9, blk, doorq = np.float32(q9), np.float32(blk).reshape(2, 13), np.float32(doorq)
+        g = redo_geometry(arm, self.ck, cyl, box, wall, q9, blk, doorq, kc)
+        ref = _oracle_cyl(g)
+        # a count that hinges on the margin: a candidate within 1e-7 of the 2 mm -- the oracle itself answers differently there
+        if len(_oracle_cyl(g, 0.002 + 1e-7)) != len(ref) or len(_oracle_cyl(g, 0.002 - 1e-7)) != len(ref):
+            self.dropped += 1
+            return
+        self.rows.append(row); self.ids.append([cyl, box, wall, 0]); self.q9.append(q9); self.blk.append(blk); self.door.append(doorq)
+        self.geo.append(g); self.ref.append(ref)
+
+    def done(self, kc):
+        n = len(self.rows)
+        assert self.dropped <= 0.02 * (n + self.dropped), (self.dropped, n)
+        return dict(ck=self.ck, kc=kc, rows=np.array(self.rows), ids=np.array(self.ids, np.int32), q9=np.stack(self.q9), blk=np.stack(self.blk),
+                    doorq=np.array(self.door, np.float32), geo=self.geo, ref=self.ref, nref=np.array([len(r) for r in self.ref]), dropped=self.dropped)
+
+
+def _free_body_walks(cs, arm, rs, row, kc, n_walks, robot_body, free_is_cyl, rows_of_state, aligned_third):
+    """a free body (the cube against the gripper base / the puck against a finger) walked in towards a robot link held at a pose
+    anywhere in the joint ranges; at first touch one case 0 - 1.5 mm deeper, and from every fourth walk one 0.3 - 2.5 mm back out"""
+    made = 0
+    while made < n_walks:
+        q9 = np.float32(np.r_[rs.uniform(JLO[:7], JHI[:7]), rs.uniform(0, 0.035, 2)])
+        pr, Rr = arm.pose(q9, robot_body)
+        quat = np.float32([0, 0, 0, 1]) if aligned_third and made % 3 == 0 else _rand_quat(rs)
+        Rf, u = quat_R64(quat), _unit(rs)
+        lateral = rs.uniform(-0.5, 0.5, 3) * (0.03 if free_is_cyl else 0.04)
+        lateral -= u * (lateral @ u)
+        sr = _support_cyl(Rr, GBASE_R, GBASE_HL, u) if robot_body == REDO_GBASE else _support_box(Rr, FINGER_H, u)
+        sf = _support_cyl(Rf, PUCK_R, PUCK_HL, u) if free_is_cyl else _support_box(Rf, CUBE_H, u)
+        slot = rows_of_state[made % len(rows_of_state)]
+
+        def state(d):
+            blk = np.stack([FAR_ROW, FAR_ROW])
+            blk[slot, 0:3] = pr + lateral + u * d
+            blk[slot, 3:7] = quat
+            return blk
+        ids = (slot, robot_body, -1) if free_is_cyl else (REDO_GBASE, slot, -1)
+
+        def count(d):
+            return len(_oracle_cyl(redo_geometry(arm, cs.ck, ids[0], ids[1], -1, q9, state(d), 0.0, kc)))
+        d = _first_touch(count, sr + sf + 0.0025)
+        if d is None:
+            continue
+        cs.add(arm, row, ids[0], ids[1], -1, q9, state(d - rs.uniform(0, 0.0015)), rs.uniform(0, 0.1), kc)
+        if made % 4 == 0:
+            cs.add(arm, row, ids[0], ids[1], -1, q9, state(d + rs.uniform(0.0003, 0.0025)), rs.uniform(0, 0.1), kc)
+        made += 1
+
+
+def _puck_static_cases(cs, arm, rs, kc):
+    q9 = Q_START
+
+    def blk_of(pos, quat):
+        blk = np.stack([FAR_ROW, FAR_ROW])
+        blk[0, 0:3], blk[0, 3:7] = pos, quat
+        return blk
+
+    def tilted():
+        tilt = 10.0 ** rs.uniform(-8, -1) * _unit(rs)[:2]
+        yaw = rs.uniform(0, 2 * np.pi)
+        quat = np.array([tilt[0] / 2, tilt[1] / 2, np.sin(yaw / 2), np.cos(yaw / 2)])
+        return np.float32(quat / np.linalg.norm(quat))
+    for trial in range(90):                             # the floor: anywhere on the 5 x 5 m plane, a third of them at its edge
+        xy = rs.uniform(-2.45, 2.45, 2)
+        if trial % 3 == 0:
+            xy[rs.randint(2)] = rs.choice([-1, 1]) * (PLANE_H[0] - rs.uniform(0, 0.04))
+        cs.add(arm, 'puck x floor', 0, REDO_STATIC, -1, q9, blk_of([xy[0], xy[1], PLANE_H[2] + PUCK_HL + rs.uniform(-2e-4, 1.5e-3)], tilted()), 0.0, kc)
+    made = 0
+    while made < 60:                                    # the table's side walls: the puck beside the table, above the switch
+        ax, sg = rs.randint(2), rs.choice([-1, 1])
+        quat = tilted() if made % 2 else _rand_quat(rs)
+        Rf = quat_R64(quat)
+        u = np.zeros(3); u[ax] = sg
+        base = SLIDE_TABLE_C.copy()
+        base[1 - ax] += rs.uniform(-0.9, 0.9) * SLIDE_TABLE_H[1 - ax]
+        base[2] = rs.uniform(0.075, 0.15)
+        base[ax] += sg * SLIDE_TABLE_H[ax]
+
+        def count(d):
+            return len(_oracle_cyl(redo_geometry(arm, cs.ck, 0, REDO_STATIC, -1, q9, blk_of(base + u * d, quat), 0.0, kc)))
+        d = _first_touch(count, _support_cyl(Rf, PUCK_R, PUCK_HL, u) + 0.0025)
+        if d is None:
+            continue
+        cs.add(arm, 'puck x table side', 0, REDO_STATIC, -1, q9, blk_of(base + u * (d - rs.uniform(0, 0.0015)), quat), 0.0, kc)
+        if made % 3 == 0:
+            cs.add(arm, 'puck x table side', 0, REDO_STATIC, -1, q9, blk_of(base + u * (d + rs.uniform(0.0003, 0.0025)), quat), 0.0, kc)
+        made += 1
+
+
+def _arm_walks(cs, arm, rs, row, kc, n_walks, cyl, box, wall):
+    """a chest pair: the robot link (a finger against the handle, the gripper base against the door / lid / a wall) brought to
+    its partner BY THE ARM -- oracle_lib.ik on targets around the partner, the pose goes through q9 -- along a random direction
+    until the oracle reports the first touch; from every walk one case 0 - 1.5 mm deeper and one 0.3 - 2.5 mm back out (out of
+    contact, within 5 mm of it).  The door joint: 0, its upper limit, anywhere between"""
+    ck = cs.ck
+    ch = MODEL['chest'][ck]
+    body = REDO_GBASE if cyl == REDO_GBASE else box
+    blk = np.stack([FAR_ROW, FAR_ROW])
+    made = tries = 0
+    while made < n_walks:
+        tries += 1
+        assert tries < 20 * n_walks, (row, made, tries)
+        doorq = np.float32((0.0, ch['upper'], rs.uniform(0, ch['upper']))[made % 3])
+        fingers = rs.uniform(0, 0.035, 2)
+        g0 = redo_geometry(arm, ck, cyl, box, wall, Q_START, blk, doorq, kc)
+        # the partner: where it is and how far it reaches along u (the link's own reach from its pose once the arm is there)
+        if cyl == REDO_HANDLE:
+            pc, reach = g0[0], lambda u: _support_cyl(g0[1], g0[2], g0[3], u)
+            inside = g0[1] @ (rs.uniform(-0.8, 0.8, 3) * [g0[2], g0[2], g0[3]])
+        else:
+            pc, reach = g0[4], lambda u: _support_box(g0[5], g0[6], u)
+            inside = rs.uniform(-0.9, 0.9, 3) * g0[6]
+        u = _unit(rs)
+        u[2] = abs(u[2])                                  # from above or from the side: the arm reaches these
+        state = dict(q=Q_START.astype(float), off=None)
+
+        def q_at(d):
+            want = pc + inside + u * d                    # where the link's centre is to be
+            for _ in range(2 if state['off'] is None else 1):
+                off = np.zeros(3) if state['off'] is None else state['off']
+                q, _ = O.ik(state['q'], want - off, max_iter=120)
+                q[7:9] = fingers
+                state['q'] = q
+                state['off'] = arm.pose(q, body)[0] - O.fk_tip(np.float32(q).astype(float))[0]
+            return np.float32(state['q'])
+
+        def count(d):
+            return len(_oracle_cyl(redo_geometry(arm, ck, cyl, box, wall, q_at(d), blk, doorq, kc)))
+        q_far = q_at(0.12)
+        pl, Rl = arm.pose(q_far, body)
+        own = _support_cyl(Rl, GBASE_R, GBASE_HL, u) if body == REDO_GBASE else _support_box(Rl, FINGER_H, u)
+        d = _first_touch(count, reach(u) - float(inside @ u) + own + 0.004)
+        if d is None:
+            continue
+        q_touch = state['q'].copy()
+        n0 = len(cs.rows)
+        cs.add(arm, row, cyl, box, wall, q_at(d - rs.uniform(0, 0.0015)), blk, doorq, kc)
+        state['q'] = q_touch
+        cs.add(arm, row, cyl, box, wall, q_at(d + rs.uniform(0.0003, 0.0025)), blk, doorq, kc)
+        made += 1
+
+
+@functools.lru_cache(None)
+def redo_pair_cases(ck):
+    """every pair cyl_redo64<ck> serves -> dict(ck, kc, rows [n] (names), ids [n][4], q9 [n][9], blk [n][2][13], doorq [n], geo (the
+    oracle-side operands), ref (the oracle's contacts), nref [n], dropped).
+    ck -1 (slide and the cube tasks): gripper base x cube, puck x finger 1 / 2, puck x floor, puck x table side wall.
+    ck 0 / 1 (the chests): gripper base x cube again, handle x finger 1 / 2, gripper base x door / lid, gripper base x every wall"""
+    arm, rs, kc = _Arm(), np.random.RandomState(100 + ck), redo_kc()
+    cs = _Cases(ck)
+    if ck <= 0:
+        _free_body_walks(cs, arm, rs, 'gripper base x cube', kc, 150, REDO_GBASE, False, (1,), True)
+    if ck < 0:
+        for f, body in enumerate((REDO_FINGER1, REDO_FINGER2)):
+            _free_body_walks(cs, arm, rs, 'puck x finger %d' % (f + 1), kc, 80, body, True, (0, 1), False)
+        _puck_static_cases(cs, arm, rs, kc)
+    else:
+        for f, body in enumerate((REDO_FINGER1, REDO_FINGER2)):
+            _arm_walks(cs, arm, rs, 'handle x finger %d' % (f + 1), kc, 36, REDO_HANDLE, body, -1)
+        _arm_walks(cs, arm, rs, 'gripper base x door', kc, 36, REDO_GBASE, REDO_DOOR, -1)
+        for w in range(len(MODEL['chest'][ck]['walls'])):
+            _arm_walks(cs, arm, rs, 'gripper base x wall %d' % w, kc, 36, REDO_GBASE, REDO_STATIC, w)
+    arm.ora.close()
+    return cs.done(kc)
+
+
+def redo_rows_expected(ck):
+    if ck < 0:
+        return {'gripper base x cube': 150, 'puck x finger 1': 75, 'puck x finger 2': 75, 'puck x floor': 80, 'puck x table side': 50}
+    out = {'handle x finger 1': 30, 'handle x finger 2': 30, 'gripper base x door': 30}
+    out.update({'gripper base x wall %d' % w: 30 for w in range(len(MODEL['chest'][ck]['walls']))})
+    if ck == 0:
+        out['gripper base x cube'] = 150
+    return out
+
+
+def _match_errors(got, ref):
+    """largest differences (normal, depth, points) with the points matched by lexsort of their positions as elsewhere; where two
+    points tie within the rounding of the sort key, by the best of the <= 24 orders"""
+    order_g, order_r = np.lexsort(got[:, :3].round(4).T), np.lexsort(ref[:, :3].round(4).T)
+    best = None
+    for perm in [order_g] + [np.array(p) for p in itertools.permutations(range(len(got)))]:
+        a, b = got[perm].astype(float), ref[order_r]
+        e = (np.abs(a[:, 6:9] - b[:, 6:9]).max(), np.abs(a[:, 9] - b[:, 9]).max(), np.abs(a[:, 0:6] - b[:, 0:6]).max())
+        if best is None or max(e[0] / REDO_BARS[0], e[1] / REDO_BARS[1], e[2] / REDO_BARS[2]) < max(best[0] / REDO_BARS[0], best[1] / REDO_BARS[1], best[2] / REDO_BARS[2]):
+            best = e
+        if max(e[0] / REDO_BARS[0], e[1] / REDO_BARS[1], e[2] / REDO_BARS[2]) < 1.0:
+            break
+    return np.array(best)
+
+
+def check_redo_pairs(ck, run, handed_bits=True):
+    """cyl_redo64<ck> on every pair it serves against the float64 oracle's cyl_box on operands assembled from the oracle and
+    model.json: the oracle's count in every case, normals and points to 1e-6, depths to 1e-8; the coverage of every row
+    (cases in contact; for the chest rows also cases out of contact) asserted.  Then the same cases with the robot body's pose
+    handed in: the same bars, and (handed_bits) the bits of the fetch-inside mode.
+    -> (largest errors (normal, depth, points), handed cases whose bits differ, per-row worst errors)"""
+    cs = redo_pair_cases(ck)
+    need = redo_rows_expected(ck)
+    ids = cs['ids'].copy()
+    mix = np.random.RandomState(3).permutation(len(ids))      # a launch that takes many cases at once gets every row in it
+    back = np.argsort(mix)
+
+    def run_mixed(ids):
+        ns, outs = run(ck, ids[mix], cs['q9'][mix], cs['blk'][mix], cs['doorq'][mix], cs['kc'])
+        return ns[back], outs[back]
+    n0, out0 = run_mixed(ids)
+    ids[:, 3] = 1
+    n1, out1 = run_mixed(ids)
+    worst, per_row, differ = np.zeros(3), {}, 0
+    for mode, (ns, outs) in enumerate(((n0, out0), (n1, out1))):
+        for i, ref in enumerate(cs['ref']):
+            row = cs['rows'][i] + (' (pose handed in)' if mode else '')
+            assert int(ns[i]) == len(ref), 'chest kind %d, %s, case %d: %d contacts, the oracle %d' % (ck, row, i, ns[i], len(ref))
+            if len(ref) == 0:
+                continue
+            e = _match_errors(outs[i].reshape(4, 10)[:len(ref)], ref)
+            assert (e < REDO_BARS).all(), 'chest kind %d, %s, case %d: normal / depth / points off by %s (bars %s)' % (ck, row, i, e, REDO_BARS)
+            worst = np.maximum(worst, e)
+            per_row[cs['rows'][i]] = np.maximum(per_row.get(cs['rows'][i], 0), e)
+    for i in range(len(ids)):
+        k = 10 * int(n0[i])
+        same = n0[i] == n1[i] and np.array_equal(out0[i][:k].view(np.uint32), out1[i][:k].view(np.uint32))
+        differ += int(not same)
+        assert same or not handed_bits, 'chest kind %d, %s, case %d: handed-in pose and fetched pose give different bits' % (ck, cs['rows'][i], i)
+        if not same:                                          # what holds where the bits may differ: the same count, the two within the bars
+            a, b = out0[i][:k].reshape(-1, 10).astype(float), out1[i][:k].reshape(-1, 10).astype(float)
+            e = np.array([np.abs(a[:, 6:9] - b[:, 6:9]).max(), np.abs(a[:, 9] - b[:, 9]).max(), np.abs(a[:, 0:6] - b[:, 0:6]).max()])
+            assert n0[i] == n1[i] and (e < REDO_BARS).all(), (ck, cs['rows'][i], i, e)
+    for row, want in need.items():
+        sel = cs['rows'] == row
+        hit, miss = int((cs['nref'][sel] > 0).sum()), int((cs['nref'][sel] == 0).sum())
+        print('chest kind %2d, %-22s in contact %3d, out of contact %3d, worst %s' % (ck, row, hit, miss, per_row.get(row)))
+        assert hit >= want, (ck, row, hit, want)
+        assert miss >= (30 if ck >= 0 and 'cube' not in row else 0 if 'floor' in row else 15), (ck, row, miss)      # (a puck on the floor is in contact)
+    assert set(cs['rows']) == set(need), set(cs['rows']) ^ set(need)
+    print('chest kind %d: %d cases, %d dropped on the margin; largest errors (normal, depth, points) %s; handed-in cases with other bits %d'
+          % (ck, len(ids), cs['dropped'], worst, differ))
+    return worst, differ, per_row
+
+
+def check_mirror_walls_are_told_apart(ck):
+    """the walls that are mirror images of each other (same half extents) get cases that another wall index cannot answer: the
+    oracle on the same pose against the other wall gives another count or contacts a millimetre away"""
+    cs = redo_pair_cases(ck)
+    walls = MODEL['chest'][ck]['walls']
+    for w, wall in enumerate(walls):
+        for v, other in enumerate(walls):
+            if v == w or other['half'] != wall['half']:
+                continue
+            told = total = 0
+            for i in np.nonzero((cs['rows'] == 'gripper base x wall %d' % w) & (cs['nref'] > 0))[0]:
+                g = list(cs['geo'][i])
+                g[4] = chest_base(ck) + np.array(other['c'])
+                alt = _oracle_cyl(g)
+                total += 1
+                told += int(len(alt) != len(cs['ref'][i]) or np.abs(alt[:, 0:3] - cs['ref'][i][:, 0:3]).max() > 1e-3)
+            assert total >= 30 and told == total, (ck, w, v, told, total)
+
+
+def check_redo_lanes(ck, run, lanes=(64, 37, 16)):
+    """a shuffled mix of all rows of one chest kind, fetched and handed-in poses alternating: with 64, 37 and 16 lanes per launch
+    every case gives, bit for bit, what it gives in a launch of its own"""
+    cs = redo_pair_cases(ck)
+    rs = np.random.RandomState(7)
+    hit, miss = np.nonzero(cs['nref'] > 0)[0], np.nonzero(cs['nref'] == 0)[0]
+    pick = np.concatenate([rs.permutation(hit)[:150], rs.permutation(miss)[:50]])
+    pick = pick[rs.permutation(len(pick))]
+    assert (cs['nref'][pick] > 0).sum() >= 100 and (cs['nref'][pick] == 0).sum() >= 30 and len(set(cs['rows'][pick])) == len(redo_rows_expected(ck))
+    ids = cs['ids'][pick].copy()
+    ids[:, 3] = np.arange(len(pick)) % 2
+    args = (ck, ids, cs['q9'][pick], cs['blk'][pick], cs['doorq'][pick], cs['kc'])
+    n1, o1 = run(*args, lanes=1)
+    assert np.array_equal(n1, cs['nref'][pick])
+    for ln in lanes:
+        n, o = run(*args, lanes=ln)
+        assert np.array_equal(n, n1), (ln, np.nonzero(n != n1)[0][:8])
+        for t in range(len(pick)):
+            k = 10 * int(n[t])
+            assert np.array_equal(o[t][:k].view(np.uint32), o1[t][:k].view(np.uint32)), (ln, t, cs['rows'][pick[t]])
+    return len(pick)
+
+
+# ---- the float pass on the shapes of those pairs
+def float_shape_pairs():
+    """(name, radius, half length, box half extents) of the cylinder x box pairs the float pass meets beyond puck x cube / table"""
+    c0, c1 = MODEL['chest']
+    out = [('gripper base x cube', GBASE_R, GBASE_HL, CUBE_H),
+           ('gripper base x door', GBASE_R, GBASE_HL, np.array(c0['door_half'])),
+           ('gripper base x lid', GBASE_R, GBASE_HL, np.array(c1['door_half'])),
+           ('gripper base x back wall', GBASE_R, GBASE_HL, np.array(c0['walls'][0]['half'])),
+           ('gripper base x side wall', GBASE_R, GBASE_HL, np.array(c0['walls'][1]['half'])),
+           ('door handle x finger', c0['handle_radius'], c0['handle_halflen'], FINGER_H),
+           ('lid handle x finger', c1['handle_radius'], c1['handle_halflen'], FINGER_H),
+           ('puck x finger', PUCK_R, PUCK_HL, FINGER_H)]
+    assert c0['walls'][1]['half'] == c0['walls'][2]['half'] == c1['walls'][2]['half'] and c0['walls'][0]['half'] == c1['walls'][0]['half'] == c1['walls'][1]['half']
+    return out
+
+
+@functools.lru_cache(None)
+def float_shape_cases():
+    """per shape pair 80 walks to the first touch (explicit poses, no arm; every fourth pair axis-aligned, every fourth tilted by
+    <= 3 degrees, the rest randomly oriented; the cylinder brought in towards a random point of the box, not only its centre),
+    each at first touch and 0.7 mm deeper -> [(name, pair [30])], float32 poses.  The pairs lie within 0.1 m of the origin, as those
+    of random_pairs_at_first_touch: 0.65 m out, where the chest stands, the oracle's own float32 mode (world coordinates
+    throughout) already strays beyond NP_STRICT from its float64 mode on 3.4 % of these pairs (43 of 1280; here 4), more than
+    check_float_shapes may set aside"""
+    from test_oracle_physics import _rot_axis
+    rs = np.random.RandomState(41)
+    out = []
+    for name, rad, hl, hb in float_shape_pairs():
+        made = 0
+        while made < 80:
+            if made % 4 == 0:
+                Ra, Rb = np.eye(3), np.eye(3)
+            elif made % 4 == 1:
+                Ra = _rot_axis(rs.normal(size=3), rs.uniform(0, 0.05))
+                Rb = _rot_axis(rs.normal(size=3), rs.uniform(0, 0.05)) @ _rot_axis(np.array([0.0, 0.0, 1.0]), rs.uniform(0, 2 * np.pi))
+            else:
+                Ra, Rb = quat_R64(_rand_quat(rs)), quat_R64(_rand_quat(rs))
+            cb, u = rs.uniform(-0.1, 0.1, 3), _unit(rs)
+            inside = Rb @ (rs.uniform(-0.9, 0.9, 3) * hb)
+            inside -= u * (inside @ u)
+
+            def count(d):
+                return len(O.cyl_box(cb + inside + u * d, Ra.ravel(), rad, hl, cb, Rb.ravel(), hb))
+            d = _first_touch(count, _support_cyl(Ra, rad, hl, u) + _support_box(Rb, hb, u) + 0.0025)
+            if d is None:
+                continue
+            for extra in (0.0, 0.0007):
+                out.append((name, pack_pair(cb + inside + u * (d - extra), Ra.ravel(), [rad, rad, hl], cb, Rb.ravel(), hb)))
+            made += 1
+    return out
+
+
+def oracle_shape_pair(pair, f32=False):
+    a = [x.astype(float) for x in unpack_pair(pair)]
+    return O.cyl_box(a[0], a[1], float(a[2][0]), float(a[2][2]), a[3], a[4], a[5], f32=f32)
+
+
+def _np_errors(got, ref):
+    order_g, order_r = np.lexsort(got[:, :3].round(4).T), np.lexsort(ref[:, :3].round(4).T)
+    g, r = got[order_g].astype(float), ref[order_r].astype(float)
+    return np.array([np.abs(g[:, 6:9] - r[:, 6:9]).max(), np.abs(g[:, 9] - r[:, 9]).max(), np.abs(g[:, 0:6] - r[:, 0:6]).max()])
+
+
+def check_float_shapes(run):
+    """cyl_box<float> on the float32 poses of the new shape pairs against the float64 oracle on the same float32 poses: the same
+    count (one more or less only where check_random_pairs accepts it: every oracle depth short of 2.1 mm), normals, depths and
+    points within NP_STRICT.  A pair on which the oracle's OWN float32 mode misses that against its float64 mode is
+    ill-conditioned by the reference's measure alone: set aside and counted, at most 1 % of the cases.
+    -> (largest errors of the checked pairs, pairs set aside, cases)"""
+    cases = float_shape_cases()
+    ns, outs, _ = run(NP_CYL, np.stack([p for _, p in cases]))
+    worst, aside, per = np.zeros(3), 0, {}
+    for i, (name, pair) in enumerate(cases):
+        ref, r32 = oracle_shape_pair(pair), oracle_shape_pair(pair, f32=True)
+        if len(r32) != len(ref) or (len(ref) and not (_np_errors(r32, ref) < NP_STRICT).all()):
+            aside += 1
+            continue
+        n = int(ns[i])
+        hit, checked = per.get(name, (0, 0))
+        if n != len(ref):
+            assert abs(n - len(ref)) <= 1 and (len(ref) == 0 or np.abs(ref[:, 9]).max() < 0.0021), '%s, case %d: %d contacts, the oracle %d' % (name, i, n, len(ref))
+            per[name] = (hit, checked)
+            continue
+        per[name] = (hit + int(n > 0), checked + 1)
+        if n == 0:
+            continue
+        e = _np_errors(outs[i].reshape(4, 10)[:n], ref)
+        assert (e < NP_STRICT).all(), '%s, case %d: normal / depth / points off by %s (bars %s)' % (name, i, e, NP_STRICT)
+        worst = np.maximum(worst, e)
+    print('float pass on %d cases of %d shape pairs: set aside %d; in contact / checked per pair %s; largest errors %s' % (len(cases), len(per), aside, per, worst))
+    assert aside <= 0.01 * len(cases), (aside, len(cases))
+    for name, _, _, _ in float_shape_pairs():
+        assert per[name][1] >= 150 and per[name][0] >= 100, (name, per[name])
+    return worst, aside, len(cases)
+
+
+# ---- the double arithmetic of the repeat
+def double_maths_inputs():
+    """squared lengths: exact 0, 4096 log-spaced and 4096 random over 1e-40 .. 1e4, exact squares, powers of two; dividends and
+    divisors of both signs over 1e-20 .. 1e4 likewise; angles: every float32 joint angle of the cases above and 4096 random in
+    [-3.06, 3.06].  Outside these ranges the routines are not meant to be used"""
+    rs = np.random.RandomState(9)
+    pw = 2.0 ** np.arange(-130, 14)
+    sq = np.concatenate([[0.0], np.logspace(-40, 4, 4096), 10.0 ** rs.uniform(-40, 4, 4096), np.arange(1, 100.0) ** 2, pw[pw >= 1e-40]])
+    mag = np.concatenate([np.logspace(-20, 4, 4096), 10.0 ** rs.uniform(-20, 4, 4096), pw[pw >= 1e-20], np.arange(1, 100.0)])
+    den = mag * rs.choice([-1.0, 1.0], len(mag))
+    num = rs.permutation(mag) * rs.choice([-1.0, 1.0], len(mag))
+    ang = [np.stack(fk64_edge_poses())[:, :7].ravel().astype(float), rs.uniform(-3.06, 3.06, 4096)]
+    ang += [redo_pair_cases(ck)['q9'][:, :7].ravel().astype(float) for ck in (-1, 0, 1)]
+    ang = np.concatenate(ang)
+    assert np.abs(ang).max() <= 3.06
+    return sq, num, den, ang
+
+
+def check_sincos64(run):
+    """sincos64 against numpy: absolute error < 1e-15 = the kernel polynomials' < 1 ulp of a result <= 1 (1.1e-16 .. 2.2e-16) +
+    the two-term reduction's half ulp of |r| <= 0.79 (5.6e-17) + numpy's own ulp (1.1e-16), ~4.5e-16, with margin"""
+    ang = double_maths_inputs()[3]
+    sn, cs = run(DM_SINCOS, ang, ang)
+    err = max(np.abs(sn - np.sin(ang)).max(), np.abs(cs - np.cos(ang)).max())
+    print('sincos64: %d angles, largest error %.3g' % (len(ang), err))
+    assert len(ang) >= 4096 + 1000 and err < 1e-15, err
+    return err
+
+
+def check_sqrt_div64(run):
+    """t_sqrt / t_div against numpy float64: relative error < 1e-15, the figure pmg_contact_body.inc states; t_sqrt(0) = 0"""
+    sq, num, den, _ = double_maths_inputs()
+    got = run(DM_SQRT, sq, sq)[0]
+    assert got[0] == 0.0 and sq[0] == 0.0
+    es = np.abs(got[1:] / np.sqrt(sq[1:]) - 1.0).max()
+    q = run(DM_DIV, num, den)[0]
+    ed = np.abs(q / (num / den) - 1.0).max()
+    ulp = 2.0 ** -52
+    print('t_sqrt: %d values, largest relative error %.3g (%.2f ulp); t_div: %d quotients, %.3g (%.2f ulp)' % (len(sq), es, es / ulp, len(num), ed, ed / ulp))
+    assert len(sq) > 8192 and len(num) > 8192 and es < 1e-15 and ed < 1e-15, (es, ed)
+    return es, ed

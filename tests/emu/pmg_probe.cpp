@@ -118,6 +118,36 @@ extern "C" int pmge_probe_cyl_redo64(int ck, int cyl_body, int box_body, int wal
     if (ck == 1) return pmg::cyl_redo64<1>(cyl_body, box_body, wall, q9, blk0, doorq, kc, prad, phl, out, W);
     return pmg::cyl_redo64<-1>(cyl_body, box_body, wall, q9, blk0, doorq, kc, prad, phl, out, W);
 }
+/* the same on any pair, with the robot body's double pose handed in (handed = 1) as spec_fk / spec_pairs do: sincos64 per arm joint into
+ * a table, fk64_chain with that table, then robot_p / robot_R.  blk0: two free-body rows.  (pmgd_cyl_redo64_pairs, gpu_probe/) */
+extern "C" int pmge_probe_cyl_redo64_pairs(int ck, int cyl_body, int box_body, int wall, int handed, const float* q9, const float* blk0, const float* doorq,
+                                           const float* kc, float prad, float phl, float* out)
+{
+    alignas(16) static float W[256];
+    const int rb = cyl_body == pmg::BODY_GBASE ? pmg::BODY_GBASE : ((box_body == pmg::BODY_FINGER1 || box_body == pmg::BODY_FINGER2) ? box_body : -1);
+    double sc[7][2], p[3], R[9];
+    const bool hand = handed && rb >= 0;
+    if (hand) {
+        for (int j = 0; j < 7; j++) pmg::sincos64((double)q9[j], sc[j][0], sc[j][1]);
+        pmg::fk64_chain(q9, sc, rb, p, R);
+    }
+    const double *hp = hand ? p : nullptr, *hR = hand ? R : nullptr;
+    if (ck == 0) return pmg::cyl_redo64<0>(cyl_body, box_body, wall, q9, blk0, doorq, kc, prad, phl, out, W, hp, hR);
+    if (ck == 1) return pmg::cyl_redo64<1>(cyl_body, box_body, wall, q9, blk0, doorq, kc, prad, phl, out, W, hp, hR);
+    return pmg::cyl_redo64<-1>(cyl_body, box_body, wall, q9, blk0, doorq, kc, prad, phl, out, W, hp, hR);
+}
+/* the double arithmetic of the repeat on arrays (pmgd_double_maths): op 0 t_sqrt(x), 1 t_div(x, y), 2 sincos64(x) -> o0, o1.  In THIS
+ * build t_sqrt / t_div are the plain operations; sincos64 is the code the device runs */
+extern "C" int pmge_probe_double_maths(int op, int n, const double* x, const double* y, double* o0, double* o1)
+{
+    if (op < 0 || op > 2 || n < 1) return -1;
+    for (int i = 0; i < n; i++) {
+        if (op == 0) o0[i] = pmg::t_sqrt(x[i]);
+        else if (op == 1) o0[i] = pmg::t_div(x[i], y[i]);
+        else pmg::sincos64(x[i], o0[i], o1[i]);
+    }
+    return 0;
+}
 extern "C" int pmge_probe_cyl_amb(const float* ca, const float* Ra, float rad, float hl, const float* cb, const float* Rb, const float* hb, float margin,
                                   float* out, float* amb_out)
 {

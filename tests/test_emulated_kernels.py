@@ -25,6 +25,7 @@ class EmuRunners:
         lib.pmge_probe_narrowphase.restype = C.c_int
         lib.pmge_probe_cyl_redo64.restype = C.c_int
         lib.pmge_probe_cyl_amb.restype = C.c_int
+        lib.pmge_probe_cyl_redo64_pairs.restype = C.c_int
 
     def dynamics(self, q, qd, tau):
         n = len(q)
@@ -68,6 +69,21 @@ class EmuRunners:
         for i in range(len(blks)):
             n[i] = self.lib.pmge_probe_cyl_redo64(-1, 0, -1, -1, _fp(q9), _fp(blks[i]), _fp(door), _fp(kc), C.c_float(0.03), C.c_float(0.01), _fp(out[i]))
         return n, out
+
+    def redo_pairs(self, ck, ids, q9, blk, doorq, kc, lanes=None):
+        n, out = np.zeros(len(ids), np.int32), np.zeros((len(ids), 40), np.float32)
+        q9, blk, kc = [np.ascontiguousarray(a, np.float32) for a in (q9, blk, kc)]
+        for i, (cyl, box, wall, handed) in enumerate(ids):
+            door = np.float32([doorq[i], 0, 0, 0])
+            n[i] = self.lib.pmge_probe_cyl_redo64_pairs(int(ck), int(cyl), int(box), int(wall), int(handed), _fp(q9[i]), _fp(blk[i]), _fp(door), _fp(kc),
+                                                        C.c_float(D.PUCK_R), C.c_float(D.PUCK_HL), _fp(out[i]))
+        return n, out
+
+    def double_maths(self, op, x, y):
+        x, y = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(y, np.float64)
+        o0, o1 = np.zeros(len(x)), np.zeros(len(x))
+        assert self.lib.pmge_probe_double_maths(op, len(x), _fp(x), _fp(y), _fp(o0), _fp(o1)) == 0
+        return o0, o1
 
 
 @pytest.fixture(scope='module')
@@ -552,3 +568,35 @@ def test_double_repeat_of_a_cylinder_pair_is_the_float64_oracle(emu_run):
     normals to 1e-6 (the outputs are float32), depths to 1e-8.  Beside it the float32 pass on float32 poses: its gross
     disagreements with the oracle are counted (the resting puck has none: the repeat is for vertex / edge contacts)."""
     D.check_cyl_redo64(emu_run.cyl_redo64, emu_run.narrowphase_amb)
+
+
+@pytest.mark.parametrize('ck', [-1, 0, 1])
+def test_double_repeat_matches_the_oracle_on_every_pair_it_serves(emu_run, ck):
+    """cyl_redo64<ck> on all six kinds of pair collide() hands it -- gripper base x cube (state row 1), puck x finger 1 / 2, puck x
+    floor and table side wall; per chest kind handle x finger 1 / 2, gripper base x door / lid and x EVERY wall, the door joint
+    at 0, at its limit and between, the arm's pose through q9 from the oracle's IK -- against the float64 oracle's cyl_box on
+    operands assembled from the oracle's link states and tests/golden/model.json: the oracle's count in every case, normals and
+    points to 1e-6, depths to 1e-8 (the g++ build measures at most 3.1e-7 / 1.5e-9 / 1.2e-7 over its 1682 cases); coverage per row asserted.  The same
+    cases with the robot body's pose handed in (spec_fk's way: sincos64 per joint, fk64_chain with the table): the same bars and
+    the same bits"""
+    D.check_redo_pairs(ck, emu_run.redo_pairs, handed_bits=True)
+    if ck >= 0:
+        D.check_mirror_walls_are_told_apart(ck)
+
+
+def test_float_pass_matches_the_oracle_on_the_shapes_of_every_cylinder_pair(emu_run):
+    """cyl_box<float> had met the puck against a cube and the table: here the gripper base (0.05 / 0.02) against a cube, the thin
+    door, the lid and both wall boxes, the two handles (0.005 / 0.01 and 0.005 / 0.025, longer than wide) and the puck against
+    the finger box -- 160 first-touch cases each, the strict narrowphase bars, pairs the oracle's own float32 mode cannot hold
+    set aside and capped at 1 % (4 of 1280; the g++ build's largest errors on the rest: 2.0e-5 normal, 4.7e-7 depth, 4.5e-7 points)"""
+    D.check_float_shapes(emu_run.narrowphase)
+
+
+def test_double_sine_and_cosine_hold_their_error_on_every_joint_angle(emu_run):
+    """sincos64 (shared code: what the device runs) against numpy on every float32 joint angle of the cases above -- limits,
+    quadrant switch points, multiples of pi / 2, each one float32 step up and down -- and 4096 random angles in [-3.06, 3.06]:
+    absolute error < 1e-15 (measured 1.1e-16).  Angles beyond 3.06 are not what the routine is for.  t_sqrt / t_div are the plain operations in
+    this build, exact by IEEE: only the gfx950 build (-m gpu) tests the Newton sequences"""
+    D.check_sincos64(emu_run.double_maths)
+    es, ed = D.check_sqrt_div64(emu_run.double_maths)
+    assert es <= 2.0 ** -52 and ed <= 2.0 ** -52

@@ -65,6 +65,20 @@ class GpuRunners:
         assert rc == 0, rc
         return n, out
 
+    def redo_pairs(self, ck, ids, q9, blk, doorq, kc, lanes=None):
+        n, out = np.zeros(len(ids), np.int32), np.zeros((len(ids), 40), np.float32)
+        rc = self.lib.pmgd_cyl_redo64_pairs(len(ids), int(ck), lanes or self.lanes, _fp(np.ascontiguousarray(ids, np.int32)), _fp(_f32(q9)), _fp(_f32(blk)),
+                                            _fp(_f32(doorq)), _fp(_f32(kc)), C.c_float(D.PUCK_R), C.c_float(D.PUCK_HL), _fp(out), _fp(n))
+        assert rc == 0, rc
+        return n, out
+
+    def double_maths(self, op, x, y):
+        x, y = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(y, np.float64)
+        o0, o1 = np.zeros(len(x)), np.zeros(len(x))
+        rc = self.lib.pmgd_double_maths(op, len(x), _fp(x), _fp(y), _fp(o0), _fp(o1))
+        assert rc == 0, rc
+        return o0, o1
+
 
 @pytest.fixture(scope='module')
 def gpu_run(built):
@@ -209,3 +223,42 @@ def test_gpu_double_repeat_with_a_chest_in_the_scene_gives_the_same_table_contac
     n1, o1 = gpu_run.cyl_redo64(blks, kc, ck=ck)
     assert np.array_equal(n0, n1) and np.array_equal(o0.view(np.uint32), o1.view(np.uint32))
     assert int((n0 > 0).sum()) > 150
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('ck', [-1, 0, 1])
+def test_gpu_double_repeat_matches_the_oracle_on_every_pair_it_serves(gpu_run, ck):
+    """cyl_redo64<ck> on the gfx950 build on all six kinds of pair collide() hands it (the cases and bars of the emulated tier:
+    the oracle's count, 1e-6 normals and points, 1e-8 depths), one case per lane, the 64 lanes of a launch carrying different
+    kinds of pair in the order the generator made them.  Then the robot body's pose handed in as spec_fk / spec_pairs do: the same
+    bars, and the bits of the fetch-inside mode."""
+    D.check_redo_pairs(ck, gpu_run.redo_pairs, handed_bits=True)
+
+
+@pytest.mark.parametrize('ck', [-1, 0, 1])
+def test_gpu_double_repeat_lanes_reproduce_what_each_pair_gives_alone(gpu_run, ck):
+    """200 cases of every row of one chest kind shuffled together (>= 100 in contact, >= 30 out of contact; fetched and handed-in
+    poses alternating), so that neighbouring lanes enter the out-of-line cyl_redo64 with different ids: with 64, 37 and 16 lanes
+    per launch every case gives, bit for bit, what it gives in a launch of its own"""
+    assert D.check_redo_lanes(ck, gpu_run.redo_pairs) >= 130
+
+
+def test_gpu_float_pass_matches_the_oracle_on_the_shapes_of_every_cylinder_pair(gpu_run):
+    """cyl_box<float> on the gfx950 build on the gripper base, both handles and the puck against the cube, door, lid, wall and
+    finger boxes (the cases, bars and the 1 % cap of the emulated tier), 64 pairs per launch"""
+    D.check_float_shapes(gpu_run.narrowphase)
+
+
+def test_gpu_double_sine_and_cosine_hold_their_error_on_every_joint_angle(gpu_run):
+    """sincos64 as hipcc compiles it against numpy: absolute error < 1e-15 on every float32 joint angle the cases here use (limits,
+    quadrant switch points, multiples of pi / 2, one float32 step to either side) and 4096 random angles in [-3.06, 3.06], the
+    range the routine is written for"""
+    D.check_sincos64(gpu_run.double_maths)
+
+
+def test_gpu_double_square_root_and_division_hold_their_stated_error(gpu_run):
+    """t_sqrt(double) / t_div(double, double) on gfx950 -- v_rsq_f64 / v_rcp_f64 and two Newton steps, code the g++ build never
+    sees -- against numpy float64: relative error < 1e-15, the figure the source states, on squared lengths 1e-40 .. 1e4 (and an
+    exact 0, which must give 0) and divisors of both signs 1e-20 .. 1e4, log-spaced, random, exact squares and powers of two.
+    Values outside these ranges are not what the routines are for"""
+    D.check_sqrt_div64(gpu_run.double_maths)

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_DIR = os.path.join(ROOT, 'gpu_probe')
 PROBE_LIBS = ['libpmg_gpu_probe.so', 'libpmg_gpu_probe_plain.so']
 PROBE_SYMBOLS = ['pmgd_variant', 'pmgd_prim', 'pmgd_prim_nin', 'pmgd_prim_nout', 'pmgd_prim_families', 'pmgd_dynamics', 'pmgd_ik',
-                 'pmgd_narrowphase', 'pmgd_fk64', 'pmgd_cyl_redo64']
+                 'pmgd_narrowphase', 'pmgd_fk64', 'pmgd_cyl_redo64', 'pmgd_cyl_redo64_pairs', 'pmgd_double_maths']
 
 
 @pytest.fixture(scope='module')
