@@ -59,7 +59,8 @@ enum {
     PMG_BUF_STATE = 8,   /* [N, 32] float32 hot state rows (q9 qd9 ee3 jt7 grip elapsed enabled resets) */
     PMG_BUF_SCHED = 9,   /* [4 + 3N + 3 ceil(N / 1024)] int32 launch schedule of the last step (diagnostics): n_prone, n_free,
                             prone list [N], free list [N], n_redo, redo list [N], then the two-pass plan's per-workgroup class
-                            counts and its promotion flag -- see DESIGN.md "launch-order plan" */
+                            counts and its promotion flag -- the layout is defined in pybullet_multigoal_gym_amd/csrc/pmg_sched.h
+                            (pmgx::Sched); see DESIGN.md 3.2 */
     PMG_BUF_ENV_CYCLES = 10 /* [N, 2] int32: shader cycles / 64 the env's wavefront spent in its last step, and the largest contact
                             count any of that step's substeps saw (envs with free objects).  Kept when the handle was created with
                             PMG_ENV_CYCLES=1 in the environment (diagnostics) AND whenever the longest-first order of the fast-path

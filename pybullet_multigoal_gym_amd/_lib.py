@@ -213,7 +213,7 @@ class PmgHandle:
 
     def schedule(self):
         """Launch schedule of the last step (diagnostics): dict(prone=[...], free=[...], redo=[...]) of env indices."""
-        n = self.N
+        n = self.N   # the one Python mirror of the layout that csrc/pmg_sched.h (pmgx::Sched) defines: counts, list 0, list 1, redo count, redo list
         buf = np.empty(3 + 3 * n, np.int32)
         self.sync()
         self.download(buf, self.device_ptr(PMG_BUF_SCHED))

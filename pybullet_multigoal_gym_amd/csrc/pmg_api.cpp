@@ -362,7 +362,7 @@ int pmg_create(const pmg_config* cfg, pmg_env** out)
     CREATE_TRY(hipMalloc((void**)&e->P.blocks, N * pmg::BLOCK_DIM * (nb ? nb : 1) * sizeof(float)));
     CREATE_TRY(hipMalloc((void**)&e->P.rng, N * 625 * sizeof(uint32_t)));
     CREATE_TRY(hipMalloc((void**)&e->P.out, N * dims.packed_dim * sizeof(float)));
-    CREATE_TRY(hipMalloc((void**)&e->P.sched, (4 + 3 * N + 3 * ((N + pmg::PLAN_THREADS - 1) / pmg::PLAN_THREADS)) * sizeof(int)));
+    CREATE_TRY(hipMalloc((void**)&e->P.sched, pmgx::Sched::words(N) * sizeof(int)));
     if (const char* pk = getenv("PMG_PACKED")) e->packed = atoi(pk) != 0;
     if (const char* tw = getenv("PMG_REACH_TWO_WAVES")) e->two_wave = atoi(tw) != 0;
     {   /* 1.5 wavefronts per SIMD of this device: how many one-env wavefronts the plan may add to a step */
@@ -433,9 +433,10 @@ int pmg_create(const pmg_config* cfg, pmg_env** out)
         CREATE_TRY(hipMemcpy(e->P.cold, cold.data(), cold.size() * sizeof(float), hipMemcpyHostToDevice));
         CREATE_TRY(hipMemcpy(e->P.blocks, blk.data(), blk.size() * sizeof(float), hipMemcpyHostToDevice));
         {   /* identity launch schedule: all envs in the contact-prone list */
-            std::vector<int> sc(4 + 3 * N + 3 * ((N + pmg::PLAN_THREADS - 1) / pmg::PLAN_THREADS), 0);   /* (+ the plan's counts and its promotion flag) */
-            sc[0] = (int)N;
-            for (size_t i = 0; i < N; i++) sc[2 + i] = (int)i;
+            std::vector<int> sc(pmgx::Sched::words(N), 0);   /* (redo list empty, nothing promoted) */
+            const pmgx::Sched S{sc.data(), (int)N};
+            S.count(0) = (int)N;
+            for (size_t i = 0; i < N; i++) S.list(0)[i] = (int)i;
             CREATE_TRY(hipMemcpy(e->P.sched, sc.data(), sc.size() * sizeof(int), hipMemcpyHostToDevice));
         }
         CREATE_TRY(hipMemset(e->P.hot, 0, N * pmg::HOT_DIM * sizeof(float)));

@@ -7,6 +7,7 @@
 #define PMG_KERNELS_H
 
 #include "pmg_contact.h"
+#include "pmg_sched.h"
 
 #ifndef PMG_COLD_CONTACTS
 #define PMG_COLD_CONTACTS 1 /* keep the reach kernel's rare contact phases out of line (compact hot loop) */
@@ -45,10 +46,7 @@ struct EnvParams {
     float* blocks;   /* [N, BLOCK_DIM * nb] */
     unsigned* rng;   /* [N, 625] MT19937 state + index */
     float* out;      /* [N, packed]: obs | policy | ag | dg | reward | goal_achieved | done */
-    int* sched;      /* [4 + 3N + 3 ceil(N / 1024)]: [0] [1] counts of {contact-prone, other} envs, [2 .. 2 + 2N) the two env
-                        lists, [2 + 2N] the redo count and behind it the redo list of the fast paths (pmg_packed.h); then
-                        [3 + 3N ..) the per-workgroup class counts of the two-pass plan (3 per 1024 envs) and one last word:
-                        did the plan promote the fingers-down class to list 0 (plan_promoted()) */
+    int* sched;      /* [Sched::words(n_envs)]: the launch schedule of the step; its layout is pmg_sched.h's, read and written through schedule() only */
     int lpt_thresh;  /* > 0 (and env_cycles kept): several blocks, fast-path list ordered longest-first -- envs whose wavefront took more than this many cycles / 64 in the PREVIOUS step lead the list (plan_class).  A constant only as an override (PMG_LPT_CYCLES) */
     int lpt_permille; /* > 0: the threshold is DERIVED ON THE DEVICE -- the cycle count above which the slowest lpt_permille / 1000 of the fast-path list's envs lay in the last step (a 128-bin histogram the plan keeps: lpt_state): no per-part, per-batch-size tuned constants */
     int lpt_parity;   /* which of the two threshold words this step's plan reads (it writes the other one for the next step) */
@@ -58,6 +56,7 @@ struct EnvParams {
 #ifdef PMG_PROFILE
     long long* prof; /* [32] per-phase shader cycles of env 0 */
 #endif
+    __host__ __device__ __forceinline__ Sched schedule() const { return Sched{sched, n_envs}; }
 };
 }  // namespace pmgx
 
@@ -202,6 +201,7 @@ __device__ __forceinline__ bool contact_prone(const EnvParams& P, const float* a
 /* one 1024-thread workgroup partitions all envs (stable, no atomics): per-wave ballots, counts of
  * every (chunk, wave) tile in LDS, then each tile scatters at its exclusive prefix */
 constexpr int PLAN_THREADS = 1024, PLAN_MAX_TILES = 1024;
+static_assert(PLAN_THREADS == pmgx::Sched::PLAN_WG, "the schedule keeps three counts per plan workgroup");
 constexpr int PLAN_SINGLE_MAX = 16384;   /* the single-workgroup plan serves batches up to here (<= PLAN_MAX_TILES * 64) */
 constexpr int PLAN_TWO_PASS_MIN = 4096;  /* ... and by default only below here: from four workgroups on the two-pass plan is the shorter one (pmg_launch_plan) */
 #ifndef PMG_FD_DIV
@@ -232,12 +232,42 @@ __device__ __forceinline__ int plan_class(const EnvParams& P, const float* actio
 {
     return plan_class(P, actions, env, plan_fetch(P, actions, env));
 }
-/* one word behind the per-workgroup counts of the two-pass plan: did the plan move the fingers-down class to list 0?
- * (then list 0 carries the long pole of the step and its wavefronts take issue priority, pmg_k_step_list) */
-__device__ __forceinline__ int* plan_promoted(const EnvParams& P)
+/* ---- what the single-workgroup plan (plan_all) and the two-pass plan (plan_count + plan_scatter) share: the promotion rule, the
+ * slot of one env and the closing writes -- so the two write the same schedule by construction.  n0 / n1 / n2: batch totals of the classes */
+/* one free object, fingers down at the table (class 1: 8 more contacts = 24 more rows per sweep): such an env holds
+ * its packed wavefront back for the whole step, alone on a wavefront it solves them in row space.  Worth a wavefront
+ * each only while they are few (pick_and_place: +12 %; push / slide, where a fifth of the batch is down there at
+ * any time: -24 %), so pick_and_place moves the whole class to the first list, behind class 0, and push / slide do not.
+ * Rounds 2-4 decided it per step from batch-wide counts (under 1 / PMG_FD_DIV of the batch AND the step within 1.5
+ * wavefronts per SIMD): the two kernels sum in different float32 orders, so an env's trajectory depended on the batch it
+ * was in -- a run on 8 GPUs was not the run on 1 GPU.  Round 5: a rule of the task (EnvParams::fd_div) */
+__device__ __forceinline__ bool plan_promote(const EnvParams& P, int n0, int n1, int n2)
 {
-    return P.sched + 3 + 3 * (size_t)P.n_envs + 3 * (size_t)((P.n_envs + 1023) / 1024);
+    return P.nb == 1 && !P.joint_control &&
+           (P.fd_div < 0 || (P.fd_div > 0 && (long long)n1 * P.fd_div <= P.n_envs && n0 + n1 + ((n2 + 3) >> 2) <= P.wave_budget));
 }
+/* one env into its list (stable: batch order within a class).  b0 / b1 / b2: envs of each class before this wavefront's, m0 / m1 / m2: the
+ * wavefront's ballots of the classes.  List 0 = class 0, then a promoted class 1; list 1 = an unpromoted class 1, then class 2.
+ * Any other class (a lane beyond the batch) writes nothing */
+__device__ __forceinline__ void plan_place(const pmgx::Sched& S, int env, int cls, bool promote, int n0, int n1, int b0, int b1, int b2,
+                                           unsigned long long m0, unsigned long long m1, unsigned long long m2)
+{
+    const unsigned long long below = (1ull << ((int)threadIdx.x & 63)) - 1ull;
+    if (cls == 0) S.at(0, b0 + __popcll(m0 & below)) = env;
+    else if (cls == 1 && promote) S.at(0, n0 + b1 + __popcll(m1 & below)) = env;
+    else if (cls == 1) S.at(1, b1 + __popcll(m1 & below)) = env;
+    else if (cls == 2) S.at(1, (promote ? 0 : n1) + b2 + __popcll(m2 & below)) = env;
+}
+/* the closing writes, by ONE thread of the plan.  (The longest-first histogram is not part of this: only the two-pass plan keeps it; that plan_all does not is a known gap, left as it is) */
+__device__ __forceinline__ void plan_commit(const pmgx::Sched& S, bool promote, int n0, int n1, int n2)
+{
+    S.count(0) = promote ? n0 + n1 : n0;
+    S.count(1) = promote ? n2 : n1 + n2;
+    S.redo_count() = 0;   /* redo list of the fast paths starts empty */
+    S.promoted() = promote ? 1 : 0;
+}
+/* the promotion flag under the free-function name that probes built against earlier versions of this header read it by */
+__device__ __forceinline__ int* plan_promoted(const EnvParams& P) { return &P.schedule().promoted(); }
 /* SIMPLE: reach under tip control -- the class is one compare on the tip target's height; its own instantiation keeps
  * the general classification (joint-control FK, object and chest tests: 5 000 instructions nobody executes for reach)
  * out of the kernel */
@@ -247,7 +277,7 @@ __device__ __forceinline__ void plan_all(const EnvParams& P, const float* action
     __shared__ int cnt0[PLAN_MAX_TILES], cnt1[PLAN_MAX_TILES], cnt2[PLAN_MAX_TILES];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = PLAN_THREADS / 64;
     const int chunks = (P.n_envs + PLAN_THREADS - 1) / PLAN_THREADS;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const pmgx::Sched S = P.schedule();
     /* every env is classified ONCE (two bits per chunk kept in a register; the second pass used to classify again: eight
      * rounds of dependent global loads for 4096 envs, 16 us), and the loads of four chunks are in flight together */
     unsigned clsbits = 0;                                   /* chunks <= PLAN_SINGLE_MAX / PLAN_THREADS = 16 */
@@ -299,41 +329,22 @@ __device__ __forceinline__ void plan_all(const EnvParams& P, const float* action
     }
     __syncthreads();
     const int n0all = tot[0], n1 = tot[1], n2all = tot[2];   /* class 2 starts behind all of class 1 in the second list */
-    /* one free object, fingers down at the table (class 1: 8 more contacts = 24 more rows per sweep): such an env holds
-     * its packed wavefront back for the whole step, alone on a wavefront it solves them in row space.  Worth a wavefront
-     * each only while they are few (pick_and_place: +12 %; push / slide, where a fifth of the batch is down there at
-     * any time: -24 %), so pick_and_place moves the whole class to the first list, behind class 0, and push / slide do not.
-     * Rounds 2-4 decided it per step from batch-wide counts (under 1 / PMG_FD_DIV of the batch AND the step within 1.5
-     * wavefronts per SIMD): the two kernels sum in different float32 orders, so an env's trajectory depended on the batch it
-     * was in -- a run on 8 GPUs was not the run on 1 GPU.  Round 5: a rule of the task (EnvParams::fd_div) */
-    const bool promote = P.nb == 1 && !P.joint_control &&
-                         (P.fd_div < 0 || (P.fd_div > 0 && (long long)n1 * P.fd_div <= P.n_envs && n0all + n1 + ((n2all + 3) >> 2) <= P.wave_budget));
+    const bool promote = plan_promote(P, n0all, n1, n2all);
     for (int c = 0; c < chunks; c++) {
         int tile = c * waves + wave;
         int env = c * PLAN_THREADS + tid;
         int cls = (env < P.n_envs && tile < PLAN_MAX_TILES) ? (c < 16 ? (int)((clsbits >> (2 * c)) & 3u) : plan_class(P, actions, env)) : 3;
         unsigned long long m0 = wv::ballot(cls == 0), m1 = wv::ballot(cls == 1), m2 = wv::ballot(cls == 2);
         const int tt = tile < tiles ? tile : 0;
-        const int b0 = cnt0[tt], b1 = cnt1[tt], b2 = cnt2[tt];
-        if (cls == 0) P.sched[2 + b0 + __popcll(m0 & below)] = env;
-        else if (cls == 1 && promote) P.sched[2 + n0all + b1 + __popcll(m1 & below)] = env;
-        else if (cls == 1) P.sched[2 + P.n_envs + b1 + __popcll(m1 & below)] = env;
-        else if (cls == 2) P.sched[2 + P.n_envs + (promote ? 0 : n1) + b2 + __popcll(m2 & below)] = env;
+        plan_place(S, env, cls, promote, n0all, n1, cnt0[tt], cnt1[tt], cnt2[tt], m0, m1, m2);
     }
-    if (tid == 0) {
-        const int n0 = n0all, n2 = n2all;
-        P.sched[0] = promote ? n0 + n1 : n0;
-        P.sched[1] = promote ? n2 : n1 + n2;
-        P.sched[2 + 2 * P.n_envs] = 0; /* redo list of the fast paths starts empty */
-        *plan_promoted(P) = promote ? 1 : 0;
-    }
+    if (tid == 0) plan_commit(S, promote, n0all, n1, n2all);
 }
 /* Batches beyond one plan workgroup (65 536 envs): the same stable three-way partition in two passes over
  * ceil(N / 1024) workgroups.  Pass 1 leaves every workgroup's class counts behind the schedule; pass 2 re-derives the
  * classes (a few loads and compares per env), turns the counts of the workgroups before it into its bases and the
  * grand totals into the promotion decision -- the SAME decision in every workgroup, so the lists come out exactly as
  * the single-workgroup plan would write them -- and scatters. */
-__device__ __forceinline__ int* plan_wg_counts(const EnvParams& P) { return P.sched + 3 + 3 * (size_t)P.n_envs; }
 __device__ __forceinline__ void plan_count(const EnvParams& P, const float* actions)
 {
     __shared__ int acc[3];
@@ -355,7 +366,7 @@ __device__ __forceinline__ void plan_count(const EnvParams& P, const float* acti
         }
     }
     __syncthreads();
-    if (tid < 3) plan_wg_counts(P)[3 * (int)blockIdx.x + tid] = acc[tid];
+    if (tid < 3) P.schedule().wg_counts()[3 * (int)blockIdx.x + tid] = acc[tid];
     if (lpt && tid < LPT_BINS && hist[tid]) atomicAdd(&P.lpt_state[2 + tid], hist[tid]);
 }
 __device__ __forceinline__ void plan_scatter(const EnvParams& P, const float* actions)
@@ -363,11 +374,11 @@ __device__ __forceinline__ void plan_scatter(const EnvParams& P, const float* ac
     __shared__ int tot[3], base[3], wcnt[3][PLAN_THREADS / 64];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = PLAN_THREADS / 64;
     const int wg = (int)blockIdx.x, nwg = (P.n_envs + PLAN_THREADS - 1) / PLAN_THREADS;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const pmgx::Sched S = P.schedule();
     if (tid < 3) { tot[tid] = 0; base[tid] = 0; }
     __syncthreads();
     {
-        const int* cnt = plan_wg_counts(P);
+        const int* cnt = S.wg_counts();
         int t0 = 0, t1 = 0, t2 = 0, b0 = 0, b1 = 0, b2 = 0;
         for (int w = tid; w < nwg; w += PLAN_THREADS) {
             const int c0 = cnt[3 * w], c1 = cnt[3 * w + 1], c2 = cnt[3 * w + 2];
@@ -383,20 +394,11 @@ __device__ __forceinline__ void plan_scatter(const EnvParams& P, const float* ac
     if (lane == 0) { wcnt[0][wave] = __popcll(m0); wcnt[1][wave] = __popcll(m1); wcnt[2][wave] = __popcll(m2); }
     __syncthreads();
     const int n0all = tot[0], n1 = tot[1], n2all = tot[2];
-    const bool promote = P.nb == 1 && !P.joint_control &&
-                         (P.fd_div < 0 || (P.fd_div > 0 && (long long)n1 * P.fd_div <= P.n_envs && n0all + n1 + ((n2all + 3) >> 2) <= P.wave_budget));
+    const bool promote = plan_promote(P, n0all, n1, n2all);
     int b0 = base[0], b1 = base[1], b2 = base[2];
     for (int w = 0; w < wave && w < waves; w++) { b0 += wcnt[0][w]; b1 += wcnt[1][w]; b2 += wcnt[2][w]; }
-    if (cls == 0) P.sched[2 + b0 + __popcll(m0 & below)] = env;
-    else if (cls == 1 && promote) P.sched[2 + n0all + b1 + __popcll(m1 & below)] = env;
-    else if (cls == 1) P.sched[2 + P.n_envs + b1 + __popcll(m1 & below)] = env;
-    else if (cls == 2) P.sched[2 + P.n_envs + (promote ? 0 : n1) + b2 + __popcll(m2 & below)] = env;
-    if (wg == 0 && tid == 0) {
-        P.sched[0] = promote ? n0all + n1 : n0all;
-        P.sched[1] = promote ? n2all : n1 + n2all;
-        P.sched[2 + 2 * P.n_envs] = 0; /* redo list of the fast paths starts empty */
-        *plan_promoted(P) = promote ? 1 : 0;
-    }
+    plan_place(S, env, cls, promote, n0all, n1, b0, b1, b2, m0, m1, m2);
+    if (wg == 0 && tid == 0) plan_commit(S, promote, n0all, n1, n2all);
     if (wg == 0 && P.nb > 1 && P.lpt_permille > 0 && P.env_cycles && P.lpt_thresh <= 0) {
         /* the NEXT step's threshold (the other parity's word: workgroups of this launch still read this step's): walk the
          * histogram of the fast-path envs' cycles from the top until the slowest lpt_permille / 1000 of them are counted */
@@ -412,11 +414,6 @@ __device__ __forceinline__ void plan_scatter(const EnvParams& P, const float* ac
             P.lpt_state[P.lpt_parity ^ 1] = (hs[0] == total) ? 0 : (b << LPT_BIN_SHIFT);   /* (nothing measured yet: off) */
         }
     }
-}
-__device__ __forceinline__ int scheduled_env(const EnvParams& P, int block)
-{
-    int n0 = P.sched[0];
-    return block < n0 ? P.sched[2 + block] : P.sched[2 + P.n_envs + (block - n0)];
 }
 
 /* ------------------------------------------------------------------ */

@@ -18,7 +18,7 @@
 template <int NB, int MAXC, int CYL>
 __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_step(pmg::EnvParams P, const float* __restrict__ actions)
 {
-    pmg::step_env<NB, MAXC, CYL>(P, actions, pmg::scheduled_env(P, (int)blockIdx.x));
+    pmg::step_env<NB, MAXC, CYL>(P, actions, P.schedule().env_of_block((int)blockIdx.x));
 }
 
 /* reach, tip control: workgroups [0, n_prone) run the contact-prone list one env per wavefront (the slow waves get the
@@ -43,9 +43,10 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_step(pmg::EnvParam
 __device__ __forceinline__ bool two_wave_step(int n_prone, int n_envs) { return n_prone > 0; }
 __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_step_reach(pmg::EnvParams P, const float* __restrict__ actions, int defer)
 {
-    const int b = (int)blockIdx.x, n0 = P.sched[0];
+    const pmgx::Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0);
     if (defer && two_wave_step(n0, P.n_envs)) return;       /* this step belongs to the two-wavefront kernel */
-    if (b < n0) pmg::step_env<0, 8, false>(P, actions, P.sched[2 + b]);
+    if (b < n0) pmg::step_env<0, 8, false>(P, actions, S.at(0, b));
     else pmgp::step_group(P, actions, b - n0);
 }
 /* The same with TWO wavefronts per workgroup, for steps that have contact-prone envs (a batched step lasts as long as
@@ -63,17 +64,29 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_st
  * launches on two streams (1.44 ms). */
 __global__ void __launch_bounds__(128, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_step_reach2(pmg::EnvParams P, const float* __restrict__ actions)
 {
-    const int b = (int)blockIdx.x, n0 = P.sched[0];
+    const pmgx::Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0);
     if (!two_wave_step(n0, P.n_envs)) return;               /* a (nearly) contact-free step: the one-wavefront kernel's turn */
-    if (b < n0) pmg::step_env<0, 8, false, true>(P, actions, P.sched[2 + b]);
+    if (b < n0) pmg::step_env<0, 8, false, true>(P, actions, S.at(0, b));
     else pmgp::step_group(P, actions, 2 * (b - n0) + ((int)threadIdx.x >> 6));
 }
-/* envs the packed path gave up on (a finger reached the table although the plan said it would not) */
+/* The redo pass: one workgroup per env of the redo list recomputes it from its untouched state with the full kernel of its task;
+ * the grid is sized for the worst case and its surplus workgroups leave on their first load */
+/* reach: envs the packed path gave up on (a finger reached the table although the plan said it would not) */
 __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_redo(pmg::EnvParams P, const float* __restrict__ actions)
 {
-    const int* redo = P.sched + 2 + 2 * P.n_envs;
-    if ((int)blockIdx.x >= redo[0]) return;
-    pmg::step_env<0, 8, false>(P, actions, redo[1 + blockIdx.x]);
+    const pmgx::Sched S = P.schedule();
+    if ((int)blockIdx.x >= S.redo_count()) return;
+    pmg::step_env<0, 8, false>(P, actions, S.redo_env(blockIdx.x));
+}
+/* free objects: <1, 24, CYL> an env with more than 12 contacts on a packed row, <5, 48, 0> / <6, 48, CYL> (chest tasks) an env of list 1
+ * whose 30-contact store, or whose ranked stage slots, overflowed */
+template <int NB, int MAXC, int CYL>
+__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_redo_env(pmg::EnvParams P, const float* __restrict__ actions)
+{
+    const pmgx::Sched S = P.schedule();
+    if ((int)blockIdx.x >= S.redo_count()) return;
+    pmg::step_env<NB, MAXC, CYL>(P, actions, S.redo_env(blockIdx.x));
 }
 
 __global__ void __launch_bounds__(1024) pmg_k_plan(pmg::EnvParams P, const float* __restrict__ actions)
@@ -234,13 +247,6 @@ __global__ void __launch_bounds__(OBJ4_THREADS, PMG_WAVES_PER_EU) pmg_k_step_obj
     __shared__ pmgp::ObjLds4 sm;
     pmgp::step_group_obj<CYL>(P, actions, (int)blockIdx.x, sm);
 }
-template <bool CYL>
-__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_redo_obj(pmg::EnvParams P, const float* __restrict__ actions)
-{
-    const int* redo = P.sched + 2 + 2 * P.n_envs;
-    if ((int)blockIdx.x >= redo[0]) return;
-    pmg::step_env<1, 24, CYL>(P, actions, redo[1 + blockIdx.x]);
-}
 /* several free blocks (block_stack / block_rearrange): list 0 = envs whose gripper works on a block, with the full
  * 48-contact store; list 1 = the rest with a 30-contact store (20 KB of LDS instead of 29: 8 workgroups per CU instead
  * of 5).  The two launches run concurrently on two streams; a list-1 env that overflows is queued for the redo pass */
@@ -248,7 +254,6 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_redo_obj(pmg::EnvP
 #define PMG_LIST_TWO_WAVES 1
 #endif
 constexpr int MULTI_SMALL_MAXC = 30;
-constexpr int LIST0_THREADS = PMG_LIST_TWO_WAVES ? 128 : 64;
 /* LIST 0 (the full contact store: the envs whose gripper works on an object -- the long pole of a batched step) runs
  * with TWO wavefronts per workgroup: the second one collides while the first computes the dynamics (helper_wave_loop) --
  * except on the lid task (chest_pick_and_place, CYL == 3): a quarter of its batch is on list 0, the step is bound by the
@@ -270,43 +275,45 @@ __global__ void __launch_bounds__(list_threads(LIST, CYL), PMG_WAVES_PER_EU) pmg
     __shared__ pmg::ContactLds<NB, MAXC> L;
     __shared__ pmg::LaneTabStore lcs;
     pmg::SpecLds<CYL>* sp = SpecStore<list_spec_wave(LIST, CYL), CYL>::get();
+    const pmgx::Sched S = P.schedule();
     const int b = (int)blockIdx.x;
-    if (b >= P.sched[LIST]) return;
+    if (b >= S.count(LIST)) return;
     /* issue priority for the wavefronts that are the long pole of the step: list 0 of the multi-block / chest tasks
      * (block_stack-4 +2.6 %), list 0 of a one-object task when the plan moved the fingers-down class there
      * (pick_and_place 1.59 -> 1.85 M; push / slide, whose long pole is the packed fingers-down wavefront, lose 3 / 8 %
      * with it and do not promote); PMG_LIST0_PRIO overrides (tools/prio_exp.sh) */
     /* ... and slide's three-wavefront list 0 (round 6): with the double repeat beside its narrowphase the pushing env is the step's
      * longest chain: 1.208 -> 1.240 M with priority (PMG_LIST0_PRIO=0 / 1, same library) */
-    if (LIST == 0) wv::set_priority(P.list0_prio >= 0 ? P.list0_prio : ((NB > 1 || list_spec_wave(LIST, CYL) || *pmg::plan_promoted(P)) ? 1 : 0));
-    const int env = P.sched[2 + LIST * P.n_envs + b];
+    if (LIST == 0) wv::set_priority(P.list0_prio >= 0 ? P.list0_prio : ((NB > 1 || list_spec_wave(LIST, CYL) || S.promoted()) ? 1 : 0));
+    const int env = S.at(LIST, b);
     const bool ok = pmg::step_env_core<NB, MAXC, CYL, list_two_waves(LIST, CYL), list_spec_wave(LIST, CYL)>(P, actions, env, L, lcs, true, sp);
-    if (!ok && threadIdx.x == 0) {
-        int* redo = P.sched + 2 + 2 * P.n_envs;
-        int slot = atomicAdd(redo, 1);
-        redo[1 + slot] = env;
-    }
-}
-__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_redo_multi(pmg::EnvParams P, const float* __restrict__ actions)
-{
-    const int* redo = P.sched + 2 + 2 * P.n_envs;
-    if ((int)blockIdx.x >= redo[0]) return;
-    pmg::step_env<5, 48, false>(P, actions, redo[1 + blockIdx.x]);
+    if (!ok && threadIdx.x == 0) S.push_redo(env);
 }
 /* chest tasks: the same two-list split -- list 0 (gripper at the chest or at a block) keeps the full layout (48 contacts,
  * a stage slot per pair, 32 000 B = 5 workgroups per CU), list 1 runs ContactLds<6, 30> with ranked stage slots
- * (CHEST_SMALL); an env of list 1 whose contacts or surviving pairs overflow is recomputed by pmg_k_redo_chest */
-template <int CYL>
-__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_redo_chest(pmg::EnvParams P, const float* __restrict__ actions)
-{
-    const int* redo = P.sched + 2 + 2 * P.n_envs;
-    if ((int)blockIdx.x >= redo[0]) return;
-    pmg::step_env<6, 48, CYL>(P, actions, redo[1 + blockIdx.x]);
-}
+ * (CHEST_SMALL); an env of list 1 whose contacts or surviving pairs overflow is recomputed by pmg_k_redo_env<6, 48, CYL> */
 /* (a redo list walked with a stride by 1024 workgroups instead of one workgroup per env leaving on its first load would save the
  * dispatch of 4096 empty workgroups, ~3 us -- but step_env inside that loop spills ~100 VGPRs to scratch, and as a noinline
  * function it needs a 500-byte frame: measured, not kept) */
 static inline int redo_grid(int n_envs) { return n_envs; }
+/* the launches of a step with two lists, one signature (Launch).  A list kernel's workgroup size is list_threads(LIST, CYL), the function in its
+ * launch bound; the grids are sized for the worst case (every env on that list) */
+typedef void (*Launch)(const pmg::EnvParams& P, const float* d_actions, hipStream_t st);
+template <int NB, int MAXC, int LIST, int CYL = 0>
+static void launch_list(const pmg::EnvParams& P, const float* d_actions, hipStream_t st)
+{
+    hipLaunchKernelGGL((pmg_k_step_list<NB, MAXC, LIST, CYL>), dim3(P.n_envs), dim3(list_threads(LIST, CYL)), 0, st, P, d_actions);
+}
+template <bool CYL>
+static void launch_obj4(const pmg::EnvParams& P, const float* d_actions, hipStream_t st)
+{
+    hipLaunchKernelGGL((pmg_k_step_obj4<CYL>), dim3((P.n_envs + 3) / 4), dim3(OBJ4_THREADS), 0, st, P, d_actions);
+}
+template <int NB, int MAXC, int CYL>
+static void launch_redo(const pmg::EnvParams& P, const float* d_actions, hipStream_t st)
+{
+    hipLaunchKernelGGL((pmg_k_redo_env<NB, MAXC, CYL>), dim3(redo_grid(P.n_envs)), dim3(64), 0, st, P, d_actions);
+}
 /* every runtime call of the fork / join between the step's two concurrent launches is checked: a failed event record or stream
  * wait would silently serialise the two lists, or let the redo pass race them -- the error goes back to the caller
  * (pmg_step*: PMG_ERR_HIP + pmg_last_error) */
@@ -327,63 +334,31 @@ hipError_t pmg_launch_step(const pmg::EnvParams& P, const float* d_actions, hipS
      * PMG_LIST0_FIRST=0 / 1 forces either order for every task (experiments) */
     static const int force_first = getenv("PMG_LIST0_FIRST") ? atoi(getenv("PMG_LIST0_FIRST")) : -1;
     const bool list0_first = force_first >= 0 ? force_first != 0 : (P.nb > 1 || P.chest >= 0 || (P.n_envs + 3) / 4 > P.wave_budget * 5 / 6);
-    if (P.chest >= 0 && packed) {
+    /* the two lists as two concurrent launches, the redo pass behind both: the side stream forks off s, list 0 goes to the stream that is
+     * submitted first, the join event is recorded behind whatever the side stream got, s waits for it and runs the redo pass */
+    auto two_lists = [&](Launch list0, Launch list1, Launch redo) -> hipError_t {
         PMG_FJ(hipEventRecord(ev_fork, s));
         PMG_FJ(hipStreamWaitEvent(side, ev_fork, 0));
-        hipStream_t s0 = list0_first ? s : side, s1 = list0_first ? side : s;
-        if (P.chest == 0) hipLaunchKernelGGL((pmg_k_step_list<6, 48, 0, 2>), dim3(P.n_envs), dim3(list_threads(0, 2)), 0, s0, P, d_actions);
-        else hipLaunchKernelGGL((pmg_k_step_list<6, 48, 0, 3>), dim3(P.n_envs), dim3(list_threads(0, 3)), 0, s0, P, d_actions);
+        list0(P, d_actions, list0_first ? s : side);
         if (!list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-        if (P.chest == 0) hipLaunchKernelGGL((pmg_k_step_list<6, MULTI_SMALL_MAXC, 1, 2>), dim3(P.n_envs), dim3(64), 0, s1, P, d_actions);
-        else hipLaunchKernelGGL((pmg_k_step_list<6, MULTI_SMALL_MAXC, 1, 3>), dim3(P.n_envs), dim3(64), 0, s1, P, d_actions);
+        list1(P, d_actions, list0_first ? side : s);
         if (list0_first) PMG_FJ(hipEventRecord(ev_join, side));
         PMG_FJ(hipStreamWaitEvent(s, ev_join, 0));
-        if (P.chest == 0) hipLaunchKernelGGL((pmg_k_redo_chest<2>), dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);
-        else hipLaunchKernelGGL((pmg_k_redo_chest<3>), dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);
+        redo(P, d_actions, s);
         return hipGetLastError();
-    }
+    };
+    if (P.chest == 0 && packed) return two_lists(launch_list<6, 48, 0, 2>, launch_list<6, MULTI_SMALL_MAXC, 1, 2>, launch_redo<6, 48, 2>);
+    if (P.chest > 0 && packed) return two_lists(launch_list<6, 48, 0, 3>, launch_list<6, MULTI_SMALL_MAXC, 1, 3>, launch_redo<6, 48, 3>);
     if (P.chest >= 0) {
         /* chest tasks: one env per wavefront with the chest layout (door slot + chest pairs, 47 KB of LDS) */
         if (P.chest == 0) hipLaunchKernelGGL((pmg_k_step<6, 48, 2>), dim3(P.n_envs), dim3(64), 0, s, P, d_actions);
         else hipLaunchKernelGGL((pmg_k_step<6, 48, 3>), dim3(P.n_envs), dim3(64), 0, s, P, d_actions);
         return hipGetLastError();
     }
-    if (P.nb > 1 && packed) {
-        PMG_FJ(hipEventRecord(ev_fork, s));
-        PMG_FJ(hipStreamWaitEvent(side, ev_fork, 0));
-        hipStream_t s0 = list0_first ? s : side, s1 = list0_first ? side : s;
-        hipLaunchKernelGGL((pmg_k_step_list<5, 48, 0>), dim3(P.n_envs), dim3(LIST0_THREADS), 0, s0, P, d_actions);
-        if (!list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-        /* up to four blocks: 24 candidate pairs instead of 32 keep the narrowphase workspace under the row store (20 KB) */
-        if (P.nb <= 4) hipLaunchKernelGGL((pmg_k_step_list<4, MULTI_SMALL_MAXC, 1>), dim3(P.n_envs), dim3(64), 0, s1, P, d_actions);
-        else hipLaunchKernelGGL((pmg_k_step_list<5, MULTI_SMALL_MAXC, 1>), dim3(P.n_envs), dim3(64), 0, s1, P, d_actions);
-        if (list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-        PMG_FJ(hipStreamWaitEvent(s, ev_join, 0));
-        hipLaunchKernelGGL(pmg_k_redo_multi, dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);
-        return hipGetLastError();
-    }
-    if (P.nb == 1 && packed) {
-        PMG_FJ(hipEventRecord(ev_fork, s));
-        PMG_FJ(hipStreamWaitEvent(side, ev_fork, 0));
-        const int groups = (P.n_envs + 3) / 4;
-        hipStream_t s0 = list0_first ? s : side, s1 = list0_first ? side : s;
-        if (P.task == PMG_TASK_SLIDE) {
-            hipLaunchKernelGGL((pmg_k_step_list<1, 24, 0, true>), dim3(P.n_envs), dim3(list_threads(0, 1)), 0, s0, P, d_actions);
-            if (!list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-            hipLaunchKernelGGL((pmg_k_step_obj4<true>), dim3(groups), dim3(OBJ4_THREADS), 0, s1, P, d_actions);
-            if (list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-            PMG_FJ(hipStreamWaitEvent(s, ev_join, 0));
-            hipLaunchKernelGGL((pmg_k_redo_obj<true>), dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);
-        } else {
-            hipLaunchKernelGGL((pmg_k_step_list<1, 24, 0, false>), dim3(P.n_envs), dim3(LIST0_THREADS), 0, s0, P, d_actions);
-            if (!list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-            hipLaunchKernelGGL((pmg_k_step_obj4<false>), dim3(groups), dim3(OBJ4_THREADS), 0, s1, P, d_actions);
-            if (list0_first) PMG_FJ(hipEventRecord(ev_join, side));
-            PMG_FJ(hipStreamWaitEvent(s, ev_join, 0));
-            hipLaunchKernelGGL((pmg_k_redo_obj<false>), dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);
-        }
-        return hipGetLastError();
-    }
+    /* up to four blocks: 24 candidate pairs instead of 32 keep the narrowphase workspace of list 1 under the row store (20 KB) */
+    if (P.nb > 1 && packed) return two_lists(launch_list<5, 48, 0>, P.nb <= 4 ? launch_list<4, MULTI_SMALL_MAXC, 1> : launch_list<5, MULTI_SMALL_MAXC, 1>, launch_redo<5, 48, 0>);
+    if (P.nb == 1 && packed && P.task == PMG_TASK_SLIDE) return two_lists(launch_list<1, 24, 0, 1>, launch_obj4<true>, launch_redo<1, 24, 1>);
+    if (P.nb == 1 && packed) return two_lists(launch_list<1, 24, 0, 0>, launch_obj4<false>, launch_redo<1, 24, 0>);
     if (P.nb == 0 && packed) {
         /* the one-wavefront kernel FIRST: when it is its turn (a contact-free step) its 1024 wavefronts are placed on an
          * empty machine, one per SIMD; behind the other kernel's draining empty workgroups they were not (0.82 ms) */

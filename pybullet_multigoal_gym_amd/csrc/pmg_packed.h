@@ -107,11 +107,10 @@ __device__ __forceinline__ void step_group(const EnvParams& P, const float* acti
 {
     __shared__ LaneTabStore lcs;
     const int l = wr::lane();
-    const int n1 = P.sched[1];
-    if (4 * group >= n1) return;                       /* wave-uniform: nothing queued for this wavefront */
-    const int idx = 4 * group + wr::row();
-    const bool have = idx < n1;                        /* surplus rows of the last wave shadow its last env and write nothing */
-    const int env = P.sched[2 + P.n_envs + (have ? idx : n1 - 1)];
+    const pmgx::Sched S = P.schedule();
+    if (4 * group >= S.count(1)) return;               /* wave-uniform: nothing queued for this wavefront */
+    bool have;                                         /* surplus rows of the last wave shadow its last env and write nothing */
+    const int env = S.packed_row(group, wr::row(), have);
 #ifdef PMG_PROFILE
     prof::begin();
 #endif
@@ -152,11 +151,7 @@ __device__ __forceinline__ void step_group(const EnvParams& P, const float* acti
 #endif
     if (!have) return;
     if (!ok) {                                         /* mispredicted: leave the state untouched, queue the env for pmg_k_redo */
-        if (l == 0) {
-            int* redo = P.sched + 2 + 2 * P.n_envs;
-            int slot = atomicAdd(redo, 1);
-            redo[1 + slot] = env;
-        }
+        if (l == 0) P.schedule().push_redo(env);          /* (a view built here: one kept live across the step costs the kernel registers) */
         return;
     }
     elapsed++;
@@ -175,7 +170,7 @@ __device__ __forceinline__ void step_group(const EnvParams& P, const float* acti
  * instead of 24.  The launch-order plan keeps envs whose gripper works on the object (tip target within 8 cm of it:
  * the only situation with more contacts) on the one-env-per-wavefront list of the same fused kernel; a substep
  * that still finds more gives the env up exactly like a mispredicted reach env: nothing is written and
- * pmg_k_redo_obj recomputes it with the full kernel. */
+ * pmg_k_redo_env<1, 24, CYL> recomputes it with the full kernel. */
 constexpr int PACKED_MAXC = 12;
 struct ObjLds4 { /* LDS of a packed workgroup: four contact stores + the lane-constant table */
     ContactLds<1, PACKED_MAXC> Ls[4];
@@ -186,17 +181,12 @@ __device__ __forceinline__ void step_group_obj(const EnvParams& P, const float* 
 {
     ContactLds<1, PACKED_MAXC>* Ls = sm.Ls;
     LaneTabStore& lcs = sm.lcs;
-    const int n1 = P.sched[1];
-    if (4 * group >= n1) return;
-    const int idx = 4 * group + wr::row();
-    const bool have = idx < n1;                        /* surplus rows shadow the last env and write nothing */
-    const int env = P.sched[2 + P.n_envs + (have ? idx : n1 - 1)];
+    const pmgx::Sched S = P.schedule();
+    if (4 * group >= S.count(1)) return;
+    bool have;                                         /* surplus rows shadow the last env and write nothing */
+    const int env = S.packed_row(group, wr::row(), have);
     const bool ok = step_env_core<1, PACKED_MAXC, CYL>(P, actions, env, Ls[wr::row()], lcs, have);
-    if (have && !ok && wr::lane() == 0) {
-        int* redo = P.sched + 2 + 2 * P.n_envs;
-        int slot = atomicAdd(redo, 1);
-        redo[1 + slot] = env;
-    }
+    if (have && !ok && wr::lane() == 0) P.schedule().push_redo(env);
 }
 
 }  // namespace pmgp

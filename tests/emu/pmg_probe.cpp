@@ -172,7 +172,7 @@ extern "C" int pmge_probe_plan(int n_envs, int nb, const float* hot, const float
     P.hot = const_cast<float*>(hot);
     P.blocks = const_cast<float*>(blocks);
     const int nwg = (n_envs + PLAN_THREADS - 1) / PLAN_THREADS;
-    std::vector<int> sc(4 + 3 * (size_t)n_envs + 3 * (size_t)nwg, -1);
+    std::vector<int> sc(pmgx::Sched::words((size_t)n_envs), -1);
     P.sched = sc.data();
     if (!two_pass) {
         if (n_envs > PLAN_MAX_TILES * 64) return -1;   /* (the launcher switches to two passes at PLAN_SINGLE_MAX already) */
@@ -181,6 +181,6 @@ extern "C" int pmge_probe_plan(int n_envs, int nb, const float* hot, const float
         emu::launch(nwg, PLAN_THREADS, [&]() { plan_count(P, actions); });
         emu::launch(nwg, PLAN_THREADS, [&]() { plan_scatter(P, actions); });
     }
-    memcpy(sched_out, sc.data(), sizeof(int) * (3 + 3 * (size_t)n_envs));
-    return *plan_promoted(P);                          /* 0 / 1: the word pmg_k_step_list reads for its issue priority */
+    memcpy(sched_out, sc.data(), sizeof(int) * (size_t)(P.schedule().wg_counts() - sc.data()));   /* counts, lists, redo count and list */
+    return P.schedule().promoted();                         /* 0 / 1: the word pmg_k_step_list reads for its issue priority */
 }

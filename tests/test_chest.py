@@ -308,7 +308,7 @@ def test_emulated_chest_two_list_split_and_redo(emu_library):
     """The chest tasks' launch plan (round 3): an env whose gripper can touch the chest or a block keeps the full layout
     (list 0: 48 contacts, a stage slot per pair), everybody else runs ContactLds<6, 30> with stage slots handed out by
     rank among the surviving pairs (list 1, 20 KB of LDS instead of 32), and a list-1 env whose contacts do not fit is
-    recomputed by pmg_k_redo_chest.  Three envs, one of each kind, against the oracle."""
+    recomputed by pmg_k_redo_env<6, 48, CYL>.  Three envs, one of each kind, against the oracle."""
     nb = 5
     env = _quiet_env('chest_push', emu_library, num_block=nb, seed=5)
     env.close()

@@ -435,7 +435,7 @@ def test_emulated_row_packed_reach_and_redo(emu_library):
 def test_emulated_row_packed_object_tasks_and_overflow_redo(emu_library):
     """push with four envs per wavefront (each row its own 12-contact store): parity with the oracle, then an env the
     plan routes to the packed list (tip TARGET 10 cm from the block) although its closed fingers are touching the
-    block on the table -- more than 12 contacts -- must be given up and recomputed by pmg_k_redo_obj."""
+    block on the table -- more than 12 contacts -- must be given up and recomputed by pmg_k_redo_env<1, 24, CYL>."""
     N = 5
     env = pmg.make_env(task='push', num_envs=N, seed=3, seed_stride=1, _library=emu_library)
     ora = O.OracleEnv('push', N, seed_base=3, seed_stride=1)

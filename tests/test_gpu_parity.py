@@ -457,7 +457,7 @@ def test_row_packed_reach_schedule_and_redo(built):
 def test_row_packed_object_overflow_goes_through_redo(built):
     """push on the device, four envs per wavefront: envs the plan leaves on the packed list (tip target 10 cm from
     the block) whose closed fingers nevertheless touch the block on the table exceed the 12-contact row store, are
-    given up and recomputed by pmg_k_redo_obj; everything still tracks the oracle."""
+    given up and recomputed by pmg_k_redo_env<1, 24, CYL>; everything still tracks the oracle."""
     N = 64
     env, ora = _pair('push', N)
     o32 = oracle_lib.FloorOracle('push', N, seed_base=0, seed_stride=1, threads=8)
@@ -807,7 +807,7 @@ def test_fast_paths_agree_with_one_env_per_wavefront(built, task, kw):
 def test_small_contact_store_overflow_goes_through_redo_multi(built):
     """block_rearrange with five blocks pushed together into a tight row on the table, gripper far away: 20 table
     contacts + 16 between neighbours exceed the 30-contact store of the fast list, so those envs must come back through
-    pmg_k_redo_multi and still track the oracle."""
+    pmg_k_redo_env<5, 48, 0> and still track the oracle."""
     import warnings
     N, nb = 32, 5
     with warnings.catch_warnings():

@@ -6,7 +6,7 @@
 #include <cstring>
 #include "pmg_kernels.h"
 template <int NB, int MAXC>
-__global__ void __launch_bounds__(64, 2) k_prof(pmg::EnvParams P, const float* act) { pmg::step_env<NB, MAXC, false>(P, act, pmg::scheduled_env(P, (int)blockIdx.x)); }
+__global__ void __launch_bounds__(64, 2) k_prof(pmg::EnvParams P, const float* act) { pmg::step_env<NB, MAXC, false>(P, act, P.schedule().env_of_block((int)blockIdx.x)); }
 __global__ void __launch_bounds__(64, 2) k_prof_packed(pmg::EnvParams P, const float* act) { long long t0 = __builtin_readcyclecounter(); pmgp::step_group(P, act, (int)blockIdx.x); long long t1 = __builtin_readcyclecounter(); if (threadIdx.x == 0) P.prof[32 + blockIdx.x] = t1 - t0; }
 __global__ void __launch_bounds__(64, 2) k_prof_obj4(pmg::EnvParams P, const float* act) { __shared__ pmgp::ObjLds4 sm; pmgp::step_group_obj<false>(P, act, (int)blockIdx.x, sm); }
 int main(int argc, char** argv)
@@ -25,7 +25,7 @@ int main(int argc, char** argv)
     for (int i = 0; i < N; i++) { for (int d = 0; d < 9; d++) hot[i * 32 + d] = q0[d]; hot[i*32+18] = -0.52f; hot[i*32+19] = 0; hot[i*32+20] = zt; hot[i*32+28] = 0.035f;
         int nbl = task == 4 ? 4 : 1; for (int b = 0; b < nbl; b++) { float* o = &blk[(i*nbl+b)*13]; o[0] = -0.45f - 0.05f*b; o[1] = 0.1f - 0.06f*b; o[2] = 0.175f; o[6] = 1.f; } }
     hipMalloc(&P.hot, hot.size()*4); hipMalloc(&P.cold, N*16*4); { std::vector<float> cold(N*16, 0.f); for (int i = 0; i < N; i++) { cold[i*16+7] = 3.f; for (int b = 0; b < 5; b++) cold[i*16+8+b] = (float)b; } hipMemcpy(P.cold, cold.data(), cold.size()*4, hipMemcpyHostToDevice); } hipMalloc(&P.goal, goal.size()*4); hipMalloc(&P.blocks, blk.size()*4); hipMalloc(&P.out, (size_t)N*P.packed*4);
-    { std::vector<int> sc(3 + 3 * N, 0); sc[1] = N; for (int i = 0; i < N; i++) sc[2 + N + i] = i; hipMalloc(&P.sched, sc.size()*4); hipMemcpy(P.sched, sc.data(), sc.size()*4, hipMemcpyHostToDevice); }
+    { std::vector<int> sc(pmgx::Sched::words(N), 0); pmgx::Sched S{sc.data(), N}; S.count(1) = N; for (int i = 0; i < N; i++) S.list(1)[i] = i; hipMalloc(&P.sched, sc.size()*4); hipMemcpy(P.sched, sc.data(), sc.size()*4, hipMemcpyHostToDevice); }
     hipMalloc(&P.prof, (32 + 8192)*8); hipMemset(P.prof, 0, (32 + 8192)*8);
     float* dact; hipMalloc(&dact, act.size()*4); hipMemcpy(dact, act.data(), act.size()*4, hipMemcpyHostToDevice);
     hipMemcpy(P.hot, hot.data(), hot.size()*4, hipMemcpyHostToDevice); hipMemcpy(P.blocks, blk.data(), blk.size()*4, hipMemcpyHostToDevice); hipMemset(P.goal, 0, goal.size()*4);
@@ -43,7 +43,7 @@ int main(int argc, char** argv)
     }
     { long long ph[32]; hipMemcpy(ph, P.prof, sizeof(ph), hipMemcpyDeviceToHost); printf("phase cycles/substep (last rep): collide-narrow %.0f compact %.0f | R1 %.0f R2 %.0f R3 %.0f R4 %.0f\n", ph[16]/100., ph[17]/100., ph[18]/100., ph[19]/100., ph[20]/100., ph[21]/100.); }
     if (task == 0) { // packed path: all envs on the free list, 4 per wave
-        std::vector<int> sc(3 + 3 * N, 0); sc[0] = 0; sc[1] = N; for (int i = 0; i < N; i++) sc[2 + N + i] = i;
+        std::vector<int> sc(pmgx::Sched::words(N), 0); pmgx::Sched S{sc.data(), N}; S.count(0) = 0; S.count(1) = N; for (int i = 0; i < N; i++) S.list(1)[i] = i;
         hipMemcpy(P.sched, sc.data(), sc.size()*4, hipMemcpyHostToDevice);
         hipMemcpy(P.hot, hot.data(), hot.size()*4, hipMemcpyHostToDevice);
         for (int rep = 0; rep < 2; rep++) { hipMemset(P.prof, 0, 32*8); hipEventRecord(a); hipLaunchKernelGGL(k_prof_packed, dim3((N+3)/4), dim3(64), 0, 0, P, dact); hipEventRecord(b); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b);
