@@ -168,6 +168,36 @@ int pmg_compute_reward(pmg_env* env, const float* achieved_goal, const float* de
 int pmg_compute_reward_device(pmg_env* env, const float* d_achieved_goal, const float* d_desired_goal,
                               int64_t batch, float* d_reward, uint8_t* d_goal_achieved);
 
+/* Running normaliser and policy-input rows of goal-conditioned learners (HER + DDPG / SAC; no reference equivalent: the
+ * reference leaves both to its caller).  A handle owns three independent normalisers of widths observation_dim,
+ * policy_state_dim and goal_dim; each keeps, in float64 on the device, the per-column sum S and sum of squares Q of the
+ * input-clipped rows it was shown and their count n, and derives in float32 mean = S/n, std = sqrt(max(eps^2,
+ * Q/n - (S/n)^2)) and inv_std = 1/std (n == 0: mean 0, std = inv_std = 1).  Sums are deterministic: their order is a
+ * function of the batch size, the width and env_index_offset alone.  Defaults: eps 0.01, clip_input
+ * 200, clip_output 5.  *_device calls are stream-ordered on the handle's stream; none of these calls reads or writes
+ * anything else of the handle. */
+enum { PMG_NORM_OBSERVATION = 0, PMG_NORM_POLICY_STATE = 1, PMG_NORM_GOAL = 2 };
+/* settings of all three normalisers (positive, finite); re-derives mean / std / inv_std, keeps the totals */
+int pmg_norm_configure(pmg_env* env, float eps, float clip_input, float clip_output);
+/* add rows [batch, D] (row_stride floats from row to row, >= D; any alignment) to normaliser `which`; d_mask: batch bytes,
+ * nonzero = take the row, or NULL = all */
+int pmg_norm_update_device(pmg_env* env, int which, const float* d_rows, int64_t row_stride, int64_t batch, const uint8_t* d_mask);
+int pmg_norm_update(pmg_env* env, int which, const float* rows, int64_t batch, const uint8_t* mask);   /* host, contiguous */
+/* observation, policy_state and desired_goal of the rows of the LAST step / reset (PMG_BUF_PACKED, read in place) into
+ * the three normalisers; d_mask: N bytes or NULL */
+int pmg_norm_update_env_device(pmg_env* env, const uint8_t* d_mask);
+/* sum [D], sumsq [D], count [1], mean / std / inv_std [D]; any pointer may be NULL; synchronous */
+int pmg_norm_read(pmg_env* env, int which, double* sum, double* sumsq, double* count, float* mean, float* std, float* inv_std);
+/* restore the totals (checkpoints); NULL totals with count 0 = reset; synchronous */
+int pmg_norm_write(pmg_env* env, int which, const double* sum, const double* sumsq, double count);
+/* d_out [batch, Ds + Dg], contiguous, state columns first: per element y = clip((clip(v, clip_input) - mean) * inv_std,
+ * clip_output) in float32; state_kind = PMG_NORM_OBSERVATION or PMG_NORM_POLICY_STATE, goals use PMG_NORM_GOAL */
+int pmg_policy_input_device(pmg_env* env, int state_kind, const float* d_state, int64_t state_stride,
+                            const float* d_goal, int64_t goal_stride, int64_t batch, float* d_out);
+int pmg_policy_input(pmg_env* env, int state_kind, const float* state, const float* goal, int64_t batch, float* out); /* host */
+/* [N, Ds + Dg] from the state and desired_goal columns of the rows of the LAST step / reset */
+int pmg_policy_input_env_device(pmg_env* env, int state_kind, float* d_out);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

@@ -17,6 +17,9 @@ PMG_BUF_PACKED = 7
 PMG_BUF_STATE = 8
 PMG_BUF_SCHED = 9
 PMG_BUF_ENV_CYCLES = 10
+PMG_NORM_OBSERVATION = 0
+PMG_NORM_POLICY_STATE = 1
+PMG_NORM_GOAL = 2
 
 
 class PmgConfig(C.Structure):
@@ -50,7 +53,9 @@ class PmgLibrary:
                'pmg_compute_reward', 'pmg_compute_reward_device', 'pmg_get_state', 'pmg_set_state', 'pmg_set_goal',
                'pmg_comm_unique_id', 'pmg_comm_init', 'pmg_allgather_packed', 'pmg_comm_overlap', 'pmg_allgather_packed_async', 'pmg_allgather_wait', 'pmg_timing_reset', 'pmg_timing_every', 'pmg_timing_read',
                'pmg_device_alloc', 'pmg_device_free', 'pmg_upload', 'pmg_download',
-               'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing']
+               'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing',
+               'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
+               'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -271,6 +276,62 @@ class PmgHandle:
         n = C.c_int64()
         self._check(self.L.lib.pmg_timing_stats(self.h, C.byref(lo), C.byref(avg), C.byref(hi), C.byref(n)))
         return lo.value, avg.value, hi.value, n.value
+
+    # -- running normaliser + policy-input rows (include/pmg.h) --
+    def norm_width(self, which):
+        d = self.dims
+        return (d.observation_dim, d.policy_state_dim, d.goal_dim)[which]
+
+    def norm_configure(self, eps=0.01, clip_input=200.0, clip_output=5.0):
+        self._check(self.L.lib.pmg_norm_configure(self.h, C.c_float(eps), C.c_float(clip_input), C.c_float(clip_output)))
+
+    def norm_update(self, which, rows, mask=None):
+        D = self.norm_width(which)
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim == 0 or rows.shape[-1] != D:
+            raise ValueError('rows %s must have a shape ending in %d' % (rows.shape, D))
+        B = rows.size // D
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(B)
+        self._check(self.L.lib.pmg_norm_update(self.h, C.c_int(which), _p(rows), C.c_int64(B), _p(m)))
+
+    def norm_update_device(self, which, d_rows_ptr, row_stride, batch, d_mask_ptr=None):
+        self._check(self.L.lib.pmg_norm_update_device(self.h, C.c_int(which), C.c_void_p(d_rows_ptr), C.c_int64(row_stride),
+                                                      C.c_int64(batch), C.c_void_p(d_mask_ptr) if d_mask_ptr else None))
+
+    def norm_update_env_device(self, d_mask_ptr=None):
+        self._check(self.L.lib.pmg_norm_update_env_device(self.h, C.c_void_p(d_mask_ptr) if d_mask_ptr else None))
+
+    def norm_read(self, which):
+        """dict(sum, sumsq [D] float64, count float, mean, std, inv_std [D] float32) of one normaliser."""
+        D = self.norm_width(which)
+        s, q, n = np.empty(D, np.float64), np.empty(D, np.float64), C.c_double()
+        mean, std, inv = np.empty(D, np.float32), np.empty(D, np.float32), np.empty(D, np.float32)
+        self._check(self.L.lib.pmg_norm_read(self.h, C.c_int(which), _p(s), _p(q), C.byref(n), _p(mean), _p(std), _p(inv)))
+        return {'sum': s, 'sumsq': q, 'count': n.value, 'mean': mean, 'std': std, 'inv_std': inv}
+
+    def norm_write(self, which, sum, sumsq, count):
+        D = self.norm_width(which)
+        s = np.ascontiguousarray(sum, np.float64).reshape(D)
+        q = np.ascontiguousarray(sumsq, np.float64).reshape(D)
+        self._check(self.L.lib.pmg_norm_write(self.h, C.c_int(which), _p(s), _p(q), C.c_double(count)))
+
+    def policy_input(self, state_kind, state, goal):
+        Ds, Dg = self.norm_width(state_kind), self.dims.goal_dim
+        state = np.ascontiguousarray(state, np.float32)
+        goal = np.ascontiguousarray(goal, np.float32)
+        if state.ndim == 0 or goal.ndim == 0 or state.shape[-1] != Ds or goal.shape[-1] != Dg or state.shape[:-1] != goal.shape[:-1]:
+            raise ValueError('state %s / goal %s must share their leading axes and end in %d / %d' % (state.shape, goal.shape, Ds, Dg))
+        B = state.size // Ds
+        out = np.empty(state.shape[:-1] + (Ds + Dg,), np.float32)
+        self._check(self.L.lib.pmg_policy_input(self.h, C.c_int(state_kind), _p(state), _p(goal), C.c_int64(B), _p(out)))
+        return out
+
+    def policy_input_device(self, state_kind, d_state_ptr, state_stride, d_goal_ptr, goal_stride, batch, d_out_ptr):
+        self._check(self.L.lib.pmg_policy_input_device(self.h, C.c_int(state_kind), C.c_void_p(d_state_ptr), C.c_int64(state_stride),
+                                                       C.c_void_p(d_goal_ptr), C.c_int64(goal_stride), C.c_int64(batch), C.c_void_p(d_out_ptr)))
+
+    def policy_input_env_device(self, state_kind, d_out_ptr):
+        self._check(self.L.lib.pmg_policy_input_env_device(self.h, C.c_int(state_kind), C.c_void_p(d_out_ptr)))
 
     def get_rng(self):
         w = np.empty((self.N, 625), np.uint32)

@@ -135,6 +135,12 @@ struct pmg_env {
     hipEvent_t ev_rows[2] = {nullptr, nullptr}, ev_gdone[2] = {nullptr, nullptr};
     bool gpending[2] = {false, false};
     int last_gather = -1;
+    /* running normalisers (pmg_norm_*): observation, policy_state, goal.  One device block each:
+     * totals double[2 D + 1] | partials double[PMG_NORM_MAX_PARTS][2 D + 1] | derived float[3 D] */
+    struct Norm { int D = 0; double* tot = nullptr; double* part = nullptr; float* der = nullptr; } norm[3];
+    float norm_eps = 0.01f, norm_clip_in = 200.f, norm_clip_out = 5.f;
+    float* d_nm_a = nullptr; float* d_nm_b = nullptr; float* d_nm_out = nullptr; unsigned char* d_nm_mask = nullptr;   /* staging of the host variants */
+    long long nm_cap = 0;
     char err[512] = "";
 };
 
@@ -449,6 +455,18 @@ int pmg_create(const pmg_config* cfg, pmg_env** out)
         }
         CREATE_TRY(hipMemset(e->P.out, 0, N * dims.packed_dim * sizeof(float)));
     }
+    for (int w = 0; w < 3; w++) {   /* normalisers start empty: n = 0, mean 0, std = inv_std = 1 */
+        pmg_env::Norm& nm = e->norm[w];
+        nm.D = w == PMG_NORM_OBSERVATION ? dims.observation_dim : (w == PMG_NORM_POLICY_STATE ? dims.policy_state_dim : dims.goal_dim);
+        const size_t P = 2 * (size_t)nm.D + 1, nd = P * (1 + PMG_NORM_MAX_PARTS);
+        CREATE_TRY(hipMalloc((void**)&nm.tot, nd * sizeof(double) + 3 * (size_t)nm.D * sizeof(float)));
+        nm.part = nm.tot + P;
+        nm.der = (float*)(nm.tot + nd);
+        std::vector<float> der(3 * (size_t)nm.D, 1.f);
+        for (int c = 0; c < nm.D; c++) der[c] = 0.f;
+        CREATE_TRY(hipMemset(nm.tot, 0, nd * sizeof(double)));
+        CREATE_TRY(hipMemcpy(nm.der, der.data(), der.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     if (upload_seeds(e) != PMG_OK) return bail(PMG_E_DEVICE);
     {   /* the tuning / experiment switches this library reads from the environment change its schedule (never its results' meaning):
          * a stray one in a user's shell -- PMG_PACKED=0 halves the throughput -- must not go unnoticed: ONE line on stderr per handle */
@@ -474,6 +492,8 @@ void pmg_destroy(pmg_env* e)
     (void)hipFree(e->P.hot); (void)hipFree(e->P.cold); (void)hipFree(e->P.goal); (void)hipFree(e->P.curr); (void)hipFree(e->P.blocks); (void)hipFree(e->P.rng); if (e->out2[1]) { (void)hipFree(e->out2[0]); (void)hipFree(e->out2[1]); } else (void)hipFree(e->P.out); (void)hipFree(e->P.sched); if (e->P.env_cycles) (void)hipFree(e->P.env_cycles); if (e->P.lpt_state) (void)hipFree(e->P.lpt_state);
     (void)hipFree(e->d_actions); (void)hipFree(e->d_mask);
     (void)hipFree(e->d_rw_ag); (void)hipFree(e->d_rw_dg); (void)hipFree(e->d_rw_r); (void)hipFree(e->d_rw_ok);
+    for (int w = 0; w < 3; w++) (void)hipFree(e->norm[w].tot);
+    (void)hipFree(e->d_nm_a); (void)hipFree(e->d_nm_b); (void)hipFree(e->d_nm_out); (void)hipFree(e->d_nm_mask);
     if (e->h_packed) (void)hipHostFree(e->h_packed);
     if (e->h_actions) (void)hipHostFree(e->h_actions);
     for (int i = 0; i < EVENT_POOL; i++) { if (e->ev_a[i]) (void)hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) (void)hipEventDestroy(e->ev_b[i]); }
@@ -675,6 +695,181 @@ int pmg_compute_reward(pmg_env* e, const float* ag, const float* dg, int64_t bat
     if (ok) HIP_TRY(e, hipMemcpyAsync(ok, e->d_rw_ok, (size_t)batch, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return PMG_OK;
+}
+
+/* ---- running normaliser + policy-input rows ---- */
+static int norm_derive_all(pmg_env* e)
+{
+    for (int w = 0; w < 3; w++) HIP_TRY(e, pmg_launch_norm_derive(e->norm[w].D, e->norm_eps, e->norm[w].tot, e->norm[w].der, e->stream));
+    return PMG_OK;
+}
+/* staging of the host variants: two input arrays, one output array of `floats` floats each and `floats` mask bytes */
+static int norm_stage(pmg_env* e, long long floats)
+{
+    if (floats <= e->nm_cap) return PMG_OK;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    (void)hipFree(e->d_nm_a); (void)hipFree(e->d_nm_b); (void)hipFree(e->d_nm_out); (void)hipFree(e->d_nm_mask);
+    e->d_nm_a = e->d_nm_b = e->d_nm_out = nullptr; e->d_nm_mask = nullptr; e->nm_cap = 0;
+    HIP_TRY(e, hipMalloc((void**)&e->d_nm_a, (size_t)floats * sizeof(float)));
+    HIP_TRY(e, hipMalloc((void**)&e->d_nm_b, (size_t)floats * sizeof(float)));
+    HIP_TRY(e, hipMalloc((void**)&e->d_nm_out, 2 * (size_t)floats * sizeof(float)));
+    HIP_TRY(e, hipMalloc((void**)&e->d_nm_mask, (size_t)floats));
+    e->nm_cap = floats;
+    return PMG_OK;
+}
+
+int pmg_norm_configure(pmg_env* e, float eps, float clip_input, float clip_output)
+{
+    if (!e) return PMG_E_INVALID;
+    if (!(eps > 0.f && clip_input > 0.f && clip_output > 0.f) || std::isinf(eps) || std::isinf(clip_input) || std::isinf(clip_output))
+        return fail(e, PMG_E_INVALID, "pmg_norm_configure: eps %g, clip_input %g and clip_output %g must be positive and finite", (double)eps, (double)clip_input, (double)clip_output);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    e->norm_eps = eps; e->norm_clip_in = clip_input; e->norm_clip_out = clip_output;
+    return norm_derive_all(e);
+}
+
+static int norm_update_rows(pmg_env* e, int which, const float* d_rows, int64_t row_stride, int64_t batch, int64_t row0, const uint8_t* d_mask)
+{
+    pmg_env::Norm& nm = e->norm[which];
+    HIP_TRY(e, pmg_launch_norm_update(d_rows, row_stride, batch, nm.D, row0, d_mask, e->norm_clip_in, e->norm_eps, nm.part, nm.tot, nm.der, e->stream));
+    return PMG_OK;
+}
+
+int pmg_norm_update_device(pmg_env* e, int which, const float* d_rows, int64_t row_stride, int64_t batch, const uint8_t* d_mask)
+{
+    if (!e) return PMG_E_INVALID;
+    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    if (!d_rows) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: d_rows is null");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: batch %lld is negative", (long long)batch);
+    if (row_stride < e->norm[which].D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: row_stride %lld is smaller than the width %d", (long long)row_stride, e->norm[which].D);
+    if (e->norm[which].D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: width %d beyond %d", e->norm[which].D, PMG_NORM_MAX_D);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return norm_update_rows(e, which, d_rows, row_stride, batch, 0, d_mask);
+}
+
+int pmg_norm_update(pmg_env* e, int which, const float* rows, int64_t batch, const uint8_t* mask)
+{
+    if (!e) return PMG_E_INVALID;
+    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_update: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    if (!rows) return fail(e, PMG_E_INVALID, "pmg_norm_update: rows is null");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_norm_update: batch %lld is negative", (long long)batch);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const int D = e->norm[which].D;
+    if (int rc = norm_stage(e, batch * D)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_nm_a, rows, (size_t)batch * D * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (mask) HIP_TRY(e, hipMemcpyAsync(e->d_nm_mask, mask, (size_t)batch, hipMemcpyHostToDevice, e->stream));
+    int rc = pmg_norm_update_device(e, which, e->d_nm_a, D, batch, mask ? e->d_nm_mask : nullptr);
+    if (rc != PMG_OK) return rc;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return PMG_OK;
+}
+
+int pmg_norm_update_env_device(pmg_env* e, const uint8_t* d_mask)
+{
+    if (!e) return PMG_E_INVALID;
+    if (!e->ever_reset) return fail(e, PMG_E_STATE, "pmg_norm_update_env_device: reset() must be called (for all envs) first");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const pmg_dims& d = e->dims;
+    const float* rows = e->P.out;   /* the buffer of the LAST step (pmg_comm_overlap: out2[out_phase]) */
+    const int off[3] = {0, d.observation_dim, d.observation_dim + d.policy_state_dim + d.goal_dim};   /* observation, policy_state, desired_goal */
+    for (int w = 0; w < 3; w++)
+        if (int rc = norm_update_rows(e, w, rows + off[w], d.packed_dim, d.num_envs, e->cfg.env_index_offset, d_mask)) return rc;
+    return PMG_OK;
+}
+
+int pmg_norm_read(pmg_env* e, int which, double* sum, double* sumsq, double* count, float* mean, float* std_, float* inv_std)
+{
+    if (!e) return PMG_E_INVALID;
+    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_read: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const pmg_env::Norm& nm = e->norm[which];
+    const size_t D = (size_t)nm.D;
+    std::vector<double> tot(2 * D + 1);
+    std::vector<float> der(3 * D);
+    HIP_TRY(e, hipMemcpyAsync(tot.data(), nm.tot, tot.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(der.data(), nm.der, der.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (sum) memcpy(sum, tot.data(), D * sizeof(double));
+    if (sumsq) memcpy(sumsq, tot.data() + D, D * sizeof(double));
+    if (count) *count = tot[2 * D];
+    if (mean) memcpy(mean, der.data(), D * sizeof(float));
+    if (std_) memcpy(std_, der.data() + D, D * sizeof(float));
+    if (inv_std) memcpy(inv_std, der.data() + 2 * D, D * sizeof(float));
+    return PMG_OK;
+}
+
+int pmg_norm_write(pmg_env* e, int which, const double* sum, const double* sumsq, double count)
+{
+    if (!e) return PMG_E_INVALID;
+    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_write: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    if (!(count >= 0.0) || std::isinf(count)) return fail(e, PMG_E_INVALID, "pmg_norm_write: count %g must be finite and >= 0", count);
+    if ((!sum || !sumsq) && count != 0.0) return fail(e, PMG_E_INVALID, "pmg_norm_write: null totals are zeros and need count == 0");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    pmg_env::Norm& nm = e->norm[which];
+    const size_t D = (size_t)nm.D;
+    std::vector<double> tot(2 * D + 1, 0.0);
+    if (sum) memcpy(tot.data(), sum, D * sizeof(double));
+    if (sumsq) memcpy(tot.data() + D, sumsq, D * sizeof(double));
+    tot[2 * D] = count;
+    HIP_TRY(e, hipMemcpyAsync(nm.tot, tot.data(), tot.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, pmg_launch_norm_derive(nm.D, e->norm_eps, nm.tot, nm.der, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return PMG_OK;
+}
+
+int pmg_policy_input_device(pmg_env* e, int state_kind, const float* d_state, int64_t state_stride, const float* d_goal,
+                            int64_t goal_stride, int64_t batch, float* d_out)
+{
+    if (!e) return PMG_E_INVALID;
+    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
+        return fail(e, PMG_E_INVALID, "pmg_policy_input_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    if (!d_state || !d_goal || !d_out) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: null pointer");
+    if (((size_t)d_out & 3) != 0) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: d_out is not aligned to a float");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: batch %lld is negative", (long long)batch);
+    const pmg_env::Norm& ns = e->norm[state_kind];
+    const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
+    if (state_stride < ns.D || goal_stride < ng.D)
+        return fail(e, PMG_E_INVALID, "pmg_policy_input_device: strides %lld / %lld are smaller than the widths %d / %d", (long long)state_stride, (long long)goal_stride, ns.D, ng.D);
+    if (ns.D > PMG_NORM_MAX_D || ng.D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: width beyond %d", PMG_NORM_MAX_D);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, pmg_launch_policy_input(d_state, state_stride, ns.D, d_goal, goal_stride, ng.D, batch, ns.der, ng.der, e->norm_clip_in, e->norm_clip_out, d_out, e->stream));
+    return PMG_OK;
+}
+
+int pmg_policy_input(pmg_env* e, int state_kind, const float* state, const float* goal, int64_t batch, float* out)
+{
+    if (!e) return PMG_E_INVALID;
+    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
+        return fail(e, PMG_E_INVALID, "pmg_policy_input: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    if (!state || !goal || !out) return fail(e, PMG_E_INVALID, "pmg_policy_input: null pointer");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_policy_input: batch %lld is negative", (long long)batch);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const int Ds = e->norm[state_kind].D, Dg = e->norm[PMG_NORM_GOAL].D;
+    if (int rc = norm_stage(e, batch * (Ds > Dg ? Ds : Dg))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->d_nm_a, state, (size_t)batch * Ds * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_nm_b, goal, (size_t)batch * Dg * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    int rc = pmg_policy_input_device(e, state_kind, e->d_nm_a, Ds, e->d_nm_b, Dg, batch, e->d_nm_out);
+    if (rc != PMG_OK) return rc;
+    HIP_TRY(e, hipMemcpyAsync(out, e->d_nm_out, (size_t)batch * (Ds + Dg) * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return PMG_OK;
+}
+
+int pmg_policy_input_env_device(pmg_env* e, int state_kind, float* d_out)
+{
+    if (!e) return PMG_E_INVALID;
+    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
+        return fail(e, PMG_E_INVALID, "pmg_policy_input_env_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    if (!d_out) return fail(e, PMG_E_INVALID, "pmg_policy_input_env_device: d_out is null");
+    if (!e->ever_reset) return fail(e, PMG_E_STATE, "pmg_policy_input_env_device: reset() must be called (for all envs) first");
+    const pmg_dims& d = e->dims;
+    const float* rows = e->P.out;   /* the buffer of the LAST step, as pmg_device_ptr(PMG_BUF_PACKED) */
+    return pmg_policy_input_device(e, state_kind, rows + (state_kind == PMG_NORM_OBSERVATION ? 0 : d.observation_dim), d.packed_dim,
+                                   rows + d.observation_dim + d.policy_state_dim + d.goal_dim, d.packed_dim, d.num_envs, d_out);
 }
 
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */

@@ -427,3 +427,172 @@ hipError_t pmg_launch_reward(const float* ag, const float* dg, long long B, int 
     }
     return hipGetLastError();
 }
+
+/* Running normaliser of HER learners: per column S = sum x', Q = sum x'^2 of the input-clipped rows and the row
+ * count n, in double.  The order of every addition is a function of (B, D, row0) alone -- no atomics: workgroup w owns the
+ * rows of chunk w (chunks are cut at multiples of `chunk` in GLOBAL row indices, `lead` = row0 % chunk), thread (j, c) adds
+ * rows j, j + J, ... of column c in ascending order (W = the power of two >= D columns side by side, J = 256 / W rows),
+ * an LDS tree folds the J row slots, and pmg_k_norm_merge adds the partial rows in index order.  Rows are read in place:
+ * any row stride, any alignment (dword loads; the goal columns of a reach packed row start at float 9). */
+__global__ void __launch_bounds__(256) pmg_k_norm_partial(const float* __restrict__ rows, long long stride, long long B, int D, int W,
+                                                         long long chunk, long long lead, const unsigned char* __restrict__ mask,
+                                                         float clip, double* __restrict__ part)
+{
+    __shared__ double ss[256], sq[256], sc[256];
+    const int t = (int)threadIdx.x, c = t & (W - 1), j = t / W, J = 256 / W;
+    long long r0 = (long long)blockIdx.x * chunk - lead, r1 = r0 + chunk;
+    if (r0 < 0) r0 = 0;
+    if (r1 > B) r1 = B;
+    double s = 0.0, q = 0.0, n = 0.0;
+    if (c < D)
+        for (long long r = r0 + j; r < r1; r += J) {
+            if (mask != nullptr && mask[r] == 0) continue;
+            const float x = fminf(fmaxf(nt::load(rows + r * stride + c), -clip), clip);
+            const double d = (double)x;
+            s += d; q += d * d; n += 1.0;
+        }
+    ss[t] = s; sq[t] = q; sc[t] = n;
+    __syncthreads();
+    for (int h = J >> 1; h >= 1; h >>= 1) {
+        if (j < h) { ss[t] += ss[t + h * W]; sq[t] += sq[t + h * W]; sc[t] += sc[t + h * W]; }
+        __syncthreads();
+    }
+    if (j == 0 && c < D) {
+        double* p = part + (size_t)blockIdx.x * (2 * D + 1);
+        p[c] = ss[t]; p[D + c] = sq[t];
+        if (c == 0) p[2 * D] = sc[t];
+    }
+}
+/* one workgroup: partial rows added in index order, then to the totals; mean | std | inv_std re-derived from the totals
+ * (nparts == 0: only that -- pmg_norm_configure, pmg_norm_write) */
+__global__ void __launch_bounds__(256) pmg_k_norm_merge(const double* __restrict__ part, int nparts, int D, double* __restrict__ tot,
+                                                       float* __restrict__ der, float eps)
+{
+    __shared__ double sn;
+    const int t = (int)threadIdx.x, P = 2 * D + 1;
+    if (t == 0) {
+        double a = 0.0;
+        for (int p = 0; p < nparts; p++) a += part[(size_t)p * P + 2 * D];
+        sn = tot[2 * D] + a;
+        tot[2 * D] = sn;
+    }
+    __syncthreads();
+    const double n = sn, e2 = (double)eps * (double)eps;
+    for (int c = t; c < D; c += 256) {
+        double s = 0.0, q = 0.0;
+        for (int p = 0; p < nparts; p++) { s += part[(size_t)p * P + c]; q += part[(size_t)p * P + D + c]; }
+        s = tot[c] + s; q = tot[D + c] + q;
+        tot[c] = s; tot[D + c] = q;
+        float mean = 0.f, sd = 1.f, inv = 1.f;
+        if (n > 0.0) {
+            const double m = s / n;
+            double var = q / n - m * m;
+            if (!(var > e2)) var = e2;
+            const double r = sqrt(var);
+            mean = (float)m; sd = (float)r; inv = (float)(1.0 / r);
+        }
+        der[c] = mean; der[D + c] = sd; der[2 * D + c] = inv;
+    }
+}
+/* Policy-input rows out[B, Ds + Dg] = clip((clip(v, clip_in) - mean) * inv_std, clip_out) of state | goal rows.  HBM-bound
+ * like the reward kernels above: 4 bytes in and 4 bytes out per element, each touched once, so every access is non-temporal.
+ * The output is ONE flat stream of B (Ds + Dg) floats: thread i of the sweep writes its float4 i (lane = consecutive 16
+ * bytes, whatever the row width) and gathers the four inputs by (row, column), which it keeps as counters: one 64-bit
+ * division per thread, none per element.  Inputs are read as dwords: rows come with any stride and alignment (in place
+ * from the packed rows).  mean / inv_std of the Ds + Dg columns sit in LDS.  The < 4 floats in front of the first 16-byte
+ * boundary of d_out and behind the last full float4 are written as dwords by workgroup 0. */
+__device__ __forceinline__ unsigned int norm_bits(float f) { unsigned int u; __builtin_memcpy(&u, &f, 4); return u; }
+__device__ __forceinline__ float policy_value(const float* __restrict__ s, long long ss, int Ds, const float* __restrict__ g, long long gs,
+                                              const float* sm, const float* si, float cin, float cout, long long row, int col)
+{
+    float v = col < Ds ? nt::load(s + row * ss + col) : nt::load(g + row * gs + (col - Ds));
+    v = fminf(fmaxf(v, -cin), cin);
+    v = (v - sm[col]) * si[col];
+    return fminf(fmaxf(v, -cout), cout);
+}
+__global__ void __launch_bounds__(256) pmg_k_policy_input(const float* __restrict__ s, long long ss, int Ds, const float* __restrict__ g,
+                                                         long long gs, int Dg, const float* __restrict__ ders,
+                                                         const float* __restrict__ derg, float cin, float cout, long long head,
+                                                         long long n4, long long total, float* __restrict__ out)
+{
+    __shared__ float sm[2 * PMG_NORM_MAX_D], si[2 * PMG_NORM_MAX_D];
+    const int W = Ds + Dg, t = (int)threadIdx.x;
+    for (int c = t; c < W; c += 256) {
+        sm[c] = c < Ds ? ders[c] : derg[c - Ds];
+        si[c] = c < Ds ? ders[2 * Ds + c] : derg[2 * Dg + (c - Ds)];
+    }
+    __syncthreads();
+    const long long sweep = (long long)gridDim.x * 256;        /* float4 per sweep of the grid */
+    long long i = (long long)blockIdx.x * 256 + t;
+    if (i < n4) {
+        const long long e = head + 4 * i;
+        long long row = e / W;
+        int col = (int)(e - row * W);
+        const long long drow = (4 * sweep) / W;
+        const int dcol = (int)(4 * sweep - drow * W);
+        float4* out4 = (float4*)(out + head);
+        for (; i < n4; i += sweep) {
+            float r[4];
+            long long rr = row;
+            int cc = col;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                r[k] = policy_value(s, ss, Ds, g, gs, sm, si, cin, cout, rr, cc);
+                if (++cc == W) { cc = 0; rr++; }
+            }
+            nt::store4(make_float4(r[0], r[1], r[2], r[3]), out4 + i);
+            row += drow; col += dcol;
+            if (col >= W) { col -= W; row++; }
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long long body_end = head + 4 * n4;
+        const int extra = (int)(head + (total - body_end));     /* < 8 */
+        if (t < extra) {
+            const long long e = t < head ? (long long)t : body_end + (t - head);
+            const long long row = e / W;
+            const int col = (int)(e - row * W);
+            nt::store(norm_bits(policy_value(s, ss, Ds, g, gs, sm, si, cin, cout, row, col)), (unsigned int*)(out + e));
+        }
+    }
+}
+static long long norm_chunk(long long B)
+{
+    /* at most PMG_NORM_MAX_PARTS - 2 chunks of a multiple of PMG_NORM_CHUNK_MIN rows (+ 1 for a leading partial chunk) */
+    const long long per = (long long)PMG_NORM_CHUNK_MIN * (PMG_NORM_MAX_PARTS - 2);
+    return PMG_NORM_CHUNK_MIN * ((B + per - 1) / per);
+}
+hipError_t pmg_launch_norm_derive(int D, float eps, double* tot, float* der, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, (const double*)nullptr, 0, D, tot, der, eps);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_norm_update(const float* d_rows, long long row_stride, long long B, int D, long long row0,
+                                  const unsigned char* d_mask, float clip_input, float eps, double* part, double* tot,
+                                  float* der, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    int W = 1;
+    while (W < D) W <<= 1;
+    const long long chunk = norm_chunk(B), lead = row0 % chunk;
+    const int nparts = (int)((lead + B + chunk - 1) / chunk);   /* <= PMG_NORM_MAX_PARTS */
+    hipLaunchKernelGGL(pmg_k_norm_partial, dim3(nparts), dim3(256), 0, s, d_rows, row_stride, B, D, W, chunk, lead, d_mask, clip_input, part);
+    hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, (const double*)part, nparts, D, tot, der, eps);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride, int Ds, const float* d_goal, long long goal_stride,
+                                   int Dg, long long B, const float* der_state, const float* der_goal, float clip_input,
+                                   float clip_output, float* d_out, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    const long long total = B * (Ds + Dg);
+    long long head = (long long)(((16 - ((size_t)d_out & 15)) & 15) / 4);
+    if (head > total) head = total;
+    const long long n4 = (total - head) / 4;
+    const long long want = (n4 + 255) / 256;
+    /* 2048 workgroups of four wavefronts fill the 256 compute units (8 wavefronts per SIMD); larger batches stride */
+    const unsigned grid = (unsigned)(want < 1 ? 1 : (want < 2048 ? want : 2048));
+    hipLaunchKernelGGL(pmg_k_policy_input, dim3(grid), dim3(256), 0, s, d_state, state_stride, Ds, d_goal, goal_stride, Dg, der_state,
+                       der_goal, clip_input, clip_output, head, n4, total, d_out);
+    return hipGetLastError();
+}

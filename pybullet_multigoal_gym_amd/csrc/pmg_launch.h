@@ -13,4 +13,20 @@ hipError_t pmg_launch_reset(const pmg::EnvParams& P, const unsigned char* d_mask
 hipError_t pmg_launch_sub_goal(const pmg::EnvParams& P, const unsigned char* d_mask, int level, hipStream_t s);
 hipError_t pmg_launch_reward(const float* ag, const float* dg, long long B, int G, float thr, int binary, float* reward,
                              unsigned char* ok, hipStream_t s);
+
+/* running normaliser + fused policy-input rows.  A normaliser of width D keeps on the device: totals
+ * double[2 D + 1] = S | Q | n, partials double[PMG_NORM_MAX_PARTS][2 D + 1] and derived float[3 D] = mean | std | inv_std */
+constexpr int PMG_NORM_MAX_PARTS = 1024;   /* partial rows of one update, whatever its batch */
+constexpr int PMG_NORM_MAX_D = 256;        /* widest row (chest tasks with joint control: 115) */
+constexpr int PMG_NORM_CHUNK_MIN = 64;     /* rows per workgroup of a small update; a multiple of it for a large one */
+/* rows [B, D] with row_stride floats between rows; row0 = global index of row 0 (chunk boundaries sit at multiples of the
+ * chunk in GLOBAL rows); S, Q, n of the unmasked rows are added to tot and der is re-derived, all behind s */
+hipError_t pmg_launch_norm_update(const float* d_rows, long long row_stride, long long B, int D, long long row0,
+                                  const unsigned char* d_mask, float clip_input, float eps, double* part, double* tot,
+                                  float* der, hipStream_t s);
+hipError_t pmg_launch_norm_derive(int D, float eps, double* tot, float* der, hipStream_t s);
+/* out[B, Ds + Dg] = clip((clip(v) - mean) * inv_std) of state | goal rows; der_* = the derived arrays of their normalisers */
+hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride, int Ds, const float* d_goal, long long goal_stride,
+                                   int Dg, long long B, const float* der_state, const float* der_goal, float clip_input,
+                                   float clip_output, float* d_out, hipStream_t s);
 #endif

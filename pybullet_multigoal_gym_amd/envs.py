@@ -268,6 +268,15 @@ class KukaVecEnv:
     def set_goal(self, goals, mask=None):
         self.handle.set_goal(goals, mask)
 
+    @property
+    def normalizer(self):
+        """The device-side running normaliser of this env's observations and goals (normalizer.Normalizer), created on
+        first access.  Not part of get_checkpoint(): it has its own state_dict()."""
+        if getattr(self, '_normalizer', None) is None:
+            from .normalizer import Normalizer
+            self._normalizer = Normalizer(self)
+        return self._normalizer
+
     def close(self):
         if not self._closed:
             self.handle.close()
