@@ -198,6 +198,57 @@ int pmg_policy_input(pmg_env* env, int state_kind, const float* state, const flo
 /* [N, Ds + Dg] from the state and desired_goal columns of the rows of the LAST step / reset */
 int pmg_policy_input_env_device(pmg_env* env, int state_kind, float* d_out);
 
+/* Hindsight-experience-replay (HER) minibatches, sampled on the device from episodes the CALLER keeps in device memory (no
+ * reference equivalent: the reference leaves replay to its caller).  The library owns no store: a rollout copies
+ * PMG_BUF_PACKED (and its actions) into its own table once per step (pmg_device_copy), and pmg_her_sample_device reads
+ * that table in place: it draws B transitions (e, t), relabels each with probability future_p by an achieved goal of a
+ * later step f of the same episode, and writes the finished minibatch: state | goal rows for t and t + 1 through the handle's
+ * normalisers, the action, and reward / flag of the (possibly relabelled) goal.  Stream-ordered on the handle's stream, no host
+ * sync; it reads the normalisers' derived values as they are on the stream at that point, writes nothing but the given
+ * outputs and touches neither the handle's state nor the envs' RNG streams.
+ *
+ * Draws, a pure function of (seed, counter, sample index b) -- sample b does not depend on B, state_kind or raw:
+ *   mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31   (mod 2^64)
+ *   GOLD = 0x9E3779B97F4A7C15; key = mix(seed ^ mix(counter + GOLD)); r_k(b) = mix(key + (4 b + k + 1) GOLD) >> 32, k = 0..3
+ *   e = (r_0 E) >> 32; t = (r_1 T) >> 32; relabelled iff (double)r_2 < (double)future_p * 2^32; f = t + 1 + ((r_3 (T - t)) >> 32)
+ * so 0 <= e < E, 0 <= t < T and t < f <= T by construction.  The multiply-shift maps 2^32 values onto n cells: a cell's
+ * probability is off 1 / n by at most 2^-32 (a relative bias of at most n / 2^32), which is accepted. */
+typedef struct pmg_her_source {      /* episodes in caller-owned device memory, read in place */
+    int32_t struct_size;
+    int32_t num_episodes;            /* E >= 1: complete episodes */
+    int32_t episode_steps;           /* T >= 1: every episode has rows 0..T and actions 0..T-1; (T + 1) E < 2^31 */
+    int32_t reserved;
+    const float* d_rows;             /* packed rows (PMG_BUF_PACKED layout, packed_dim floats): row (e, t) at
+                                        d_rows + e * row_episode_stride + t * row_time_stride */
+    int64_t row_episode_stride, row_time_stride;        /* in floats, >= packed_dim; 0 only where the extent is 1 (E == 1) */
+    const float* d_actions;          /* action (e, t), action_dim floats; may be NULL when d_action is NULL */
+    int64_t action_episode_stride, action_time_stride;  /* in floats, >= action_dim; 0 only where the extent is 1 */
+} pmg_her_source;
+
+typedef struct pmg_her_batch {
+    int32_t struct_size;
+    int32_t state_kind;              /* PMG_NORM_OBSERVATION or PMG_NORM_POLICY_STATE */
+    int32_t raw;                     /* 0: rows through the handle's normalisers exactly as pmg_policy_input_device;
+                                        1: bit copies of state | goal, no clip, no normalisation */
+    float   future_p;                /* in [0, 1]; HER's k / (k + 1), usually 0.8 */
+    uint64_t seed, counter;          /* the draws are a pure function of (seed, counter, sample index) */
+    int64_t batch;                   /* B >= 0; 0 is a successful no-op */
+    float* d_x;                      /* [B, Ds + Dg]  state(e, t)     | g'   -- every output may be NULL */
+    float* d_x_next;                 /* [B, Ds + Dg]  state(e, t + 1) | g' */
+    float* d_action;                 /* [B, action_dim] */
+    float* d_reward;                 /* [B]  reward of (achieved_goal(e, t + 1), g'), as pmg_compute_reward */
+    uint8_t* d_goal_achieved;        /* [B] */
+    int32_t* d_index;                /* [B, 3]: e, t, f (f = -1 where the goal was not relabelled) */
+} pmg_her_batch;
+/* g' = achieved_goal(e, f) where the sample was relabelled, desired_goal(e, t) otherwise; reward and flag use the handle's
+ * binary_reward and distance_threshold.  Both strides given, a table may be time-major [T + 1, E, P] (one pmg_device_copy
+ * of PMG_BUF_PACKED per step) or episode-major [E, T + 1, P], padded or not; inputs and outputs may have any 4-byte
+ * alignment.  PMG_E_INVALID (nothing launched): wrong struct_size, E < 1, T < 1, (T + 1) E >= 2^31, B < 0, d_rows NULL, a
+ * stride too small, state_kind not a state kind, future_p outside [0, 1] or NaN, d_action without d_actions.  With d_index
+ * NULL the indices go to scratch of the handle, sized at the first call (a later LARGER batch re-sizes it, which waits
+ * for the stream once). */
+int pmg_her_sample_device(pmg_env* env, const pmg_her_source* src, const pmg_her_batch* out);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */
@@ -251,6 +302,9 @@ int pmg_device_alloc(pmg_env* env, uint64_t bytes, void** d_ptr);
 int pmg_device_free(pmg_env* env, void* d_ptr);
 int pmg_upload(pmg_env* env, void* d_dst, const void* h_src, uint64_t bytes);   /* synchronous at return */
 int pmg_download(pmg_env* env, void* h_dst, const void* d_src, uint64_t bytes); /* synchronous at return */
+/* device to device, stream-ordered on the handle's stream (no host sync): how such a caller records PMG_BUF_PACKED rows of
+ * a step into its own episode table (pmg_her_sample_device) */
+int pmg_device_copy(pmg_env* env, void* d_dst, const void* d_src, uint64_t bytes);
 
 /* Kernel timing of the most recent *_device call sequence: HIP events on the
  * handle's stream bracket every step kernel; returns average ms per launch

@@ -37,6 +37,19 @@ class PmgDims(C.Structure):
                 ('packed_dim', C.c_int32), ('reserved', C.c_int32)]
 
 
+class PmgHerSource(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('num_episodes', C.c_int32), ('episode_steps', C.c_int32), ('reserved', C.c_int32),
+                ('d_rows', C.c_void_p), ('row_episode_stride', C.c_int64), ('row_time_stride', C.c_int64),
+                ('d_actions', C.c_void_p), ('action_episode_stride', C.c_int64), ('action_time_stride', C.c_int64)]
+
+
+class PmgHerBatch(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('state_kind', C.c_int32), ('raw', C.c_int32), ('future_p', C.c_float),
+                ('seed', C.c_uint64), ('counter', C.c_uint64), ('batch', C.c_int64),
+                ('d_x', C.c_void_p), ('d_x_next', C.c_void_p), ('d_action', C.c_void_p), ('d_reward', C.c_void_p),
+                ('d_goal_achieved', C.c_void_p), ('d_index', C.c_void_p)]
+
+
 class PmgError(RuntimeError):
     pass
 
@@ -55,7 +68,8 @@ class PmgLibrary:
                'pmg_device_alloc', 'pmg_device_free', 'pmg_upload', 'pmg_download',
                'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing',
                'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
-               'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device']
+               'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
+               'pmg_her_sample_device', 'pmg_device_copy']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -256,6 +270,26 @@ class PmgHandle:
     def download(self, array, d_ptr):
         assert array.flags['C_CONTIGUOUS']
         self._check(self.L.lib.pmg_download(self.h, _p(array), C.c_void_p(d_ptr), C.c_uint64(array.nbytes)))
+
+    def device_copy(self, d_dst_ptr, d_src_ptr, nbytes):
+        """Device to device on the handle's stream, no host sync (how a rollout records PMG_BUF_PACKED rows for her_sample_device)."""
+        self._check(self.L.lib.pmg_device_copy(self.h, C.c_void_p(d_dst_ptr), C.c_void_p(d_src_ptr), C.c_uint64(nbytes)))
+
+    # -- HER minibatches from caller-owned episode rows (include/pmg.h, DESIGN.md 3.8) --
+    def her_structs(self, d_rows, num_episodes, episode_steps, row_episode_stride, row_time_stride, batch, d_actions=None,
+                    action_episode_stride=0, action_time_stride=0, state_kind=PMG_NORM_POLICY_STATE, raw=False, future_p=0.8,
+                    seed=0, counter=0, d_x=None, d_x_next=None, d_action=None, d_reward=None, d_goal_achieved=None, d_index=None):
+        """The two argument structs of pmg_her_sample_device (pointers as integers or None)."""
+        src = PmgHerSource(C.sizeof(PmgHerSource), num_episodes, episode_steps, 0, d_rows, row_episode_stride, row_time_stride,
+                           d_actions, action_episode_stride, action_time_stride)
+        out = PmgHerBatch(C.sizeof(PmgHerBatch), state_kind, int(bool(raw)), future_p, seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), batch,
+                          d_x, d_x_next, d_action, d_reward, d_goal_achieved, d_index)
+        return src, out
+
+    def her_sample_device(self, *args, **kw):
+        """pmg_her_sample_device with the arguments of her_structs(); stream-ordered, no host sync."""
+        src, out = self.her_structs(*args, **kw)
+        self._check(self.L.lib.pmg_her_sample_device(self.h, C.byref(src), C.byref(out)))
 
     def timing_reset(self):
         self._check(self.L.lib.pmg_timing_reset(self.h))

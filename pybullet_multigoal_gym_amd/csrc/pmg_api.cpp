@@ -141,6 +141,8 @@ struct pmg_env {
     float norm_eps = 0.01f, norm_clip_in = 200.f, norm_clip_out = 5.f;
     float* d_nm_a = nullptr; float* d_nm_b = nullptr; float* d_nm_out = nullptr; unsigned char* d_nm_mask = nullptr;   /* staging of the host variants */
     long long nm_cap = 0;
+    int* d_her_idx = nullptr;         /* e, t, f of a pmg_her_sample_device batch whose caller passed no d_index */
+    long long her_cap = 0;            /* samples it holds */
     char err[512] = "";
 };
 
@@ -494,6 +496,7 @@ void pmg_destroy(pmg_env* e)
     (void)hipFree(e->d_rw_ag); (void)hipFree(e->d_rw_dg); (void)hipFree(e->d_rw_r); (void)hipFree(e->d_rw_ok);
     for (int w = 0; w < 3; w++) (void)hipFree(e->norm[w].tot);
     (void)hipFree(e->d_nm_a); (void)hipFree(e->d_nm_b); (void)hipFree(e->d_nm_out); (void)hipFree(e->d_nm_mask);
+    (void)hipFree(e->d_her_idx);
     if (e->h_packed) (void)hipHostFree(e->h_packed);
     if (e->h_actions) (void)hipHostFree(e->h_actions);
     for (int i = 0; i < EVENT_POOL; i++) { if (e->ev_a[i]) (void)hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) (void)hipEventDestroy(e->ev_b[i]); }
@@ -872,6 +875,64 @@ int pmg_policy_input_env_device(pmg_env* e, int state_kind, float* d_out)
                                    rows + d.observation_dim + d.policy_state_dim + d.goal_dim, d.packed_dim, d.num_envs, d_out);
 }
 
+/* ---- HER minibatches from caller-owned episode rows ---- */
+/* a stride of `extent` items of `width` floats: at least the width, or 0 where there is one item only */
+static bool her_stride_ok(int64_t stride, int64_t extent, int width) { return stride >= width || (stride == 0 && extent == 1); }
+
+int pmg_her_sample_device(pmg_env* e, const pmg_her_source* src, const pmg_her_batch* out)
+{
+    if (!e) return PMG_E_INVALID;
+    if (!src || !out) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: null argument");
+    if (src->struct_size != (int32_t)sizeof(pmg_her_source) || out->struct_size != (int32_t)sizeof(pmg_her_batch))
+        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: struct_size %d / %d != %zu / %zu", src->struct_size, out->struct_size, sizeof(pmg_her_source), sizeof(pmg_her_batch));
+    const pmg_dims& d = e->dims;
+    const int64_t E = src->num_episodes, T = src->episode_steps, B = out->batch;
+    if (E < 1 || T < 1) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: num_episodes %lld and episode_steps %lld must be >= 1", (long long)E, (long long)T);
+    if ((T + 1) * E >= (1ll << 31)) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: (episode_steps + 1) * num_episodes = %lld must stay below 2^31", (long long)((T + 1) * E));
+    if (B < 0) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: batch %lld is negative", (long long)B);
+    if (!src->d_rows) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: d_rows is null");
+    if (!her_stride_ok(src->row_episode_stride, E, d.packed_dim) || !her_stride_ok(src->row_time_stride, T + 1, d.packed_dim))
+        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: row strides %lld / %lld are smaller than packed_dim %d", (long long)src->row_episode_stride, (long long)src->row_time_stride, d.packed_dim);
+    if (out->d_action && !src->d_actions) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: d_action needs d_actions");
+    if (src->d_actions && (!her_stride_ok(src->action_episode_stride, E, d.action_dim) || !her_stride_ok(src->action_time_stride, T, d.action_dim)))
+        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: action strides %lld / %lld are smaller than action_dim %d", (long long)src->action_episode_stride, (long long)src->action_time_stride, d.action_dim);
+    if (out->state_kind != PMG_NORM_OBSERVATION && out->state_kind != PMG_NORM_POLICY_STATE)
+        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", out->state_kind);
+    if (!(out->future_p >= 0.f && out->future_p <= 1.f)) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: future_p %g is outside [0, 1]", (double)out->future_p);
+    if ((((size_t)src->d_rows | (size_t)src->d_actions | (size_t)out->d_x | (size_t)out->d_x_next | (size_t)out->d_action | (size_t)out->d_reward | (size_t)out->d_index) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: a float / int32 pointer is not aligned to 4 bytes");
+    const pmg_env::Norm& ns = e->norm[out->state_kind];
+    const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
+    if (ns.D > PMG_NORM_MAX_D || ng.D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: width beyond %d", PMG_NORM_MAX_D);
+    if (B == 0 || !(out->d_x || out->d_x_next || out->d_action || out->d_reward || out->d_goal_achieved || out->d_index)) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    int* idx = out->d_index;
+    if (!idx && (out->d_x || out->d_x_next)) {
+        if (B > e->her_cap) {   /* sized at the first call; a larger batch later waits for the stream once */
+            HIP_TRY(e, hipStreamSynchronize(e->stream));
+            (void)hipFree(e->d_her_idx);
+            e->d_her_idx = nullptr; e->her_cap = 0;
+            if (hipMalloc((void**)&e->d_her_idx, (size_t)B * 3 * sizeof(int)) != hipSuccess) return fail(e, PMG_E_NOMEM, "pmg_her_sample_device: no memory for %lld index rows", (long long)B);
+            e->her_cap = B;
+        }
+        idx = e->d_her_idx;
+    }
+    PmgHer H;
+    H.rows = src->d_rows; H.res = src->row_episode_stride; H.rts = src->row_time_stride;
+    H.act = src->d_actions; H.aes = src->action_episode_stride; H.ats = src->action_time_stride;
+    H.E = (int)E; H.T = (int)T; H.A = d.action_dim; H.Ds = ns.D; H.G = d.goal_dim;
+    H.so = out->state_kind == PMG_NORM_OBSERVATION ? 0 : d.observation_dim;
+    H.ago = d.observation_dim + d.policy_state_dim; H.dgo = H.ago + d.goal_dim;
+    H.raw = out->raw != 0; H.binary = e->cfg.binary_reward;
+    H.thr = e->cfg.distance_threshold; H.cin = e->norm_clip_in; H.cout = e->norm_clip_out;
+    H.seed = out->seed; H.counter = out->counter;
+    H.relabel_below = (unsigned long long)ceil((double)out->future_p * 4294967296.0);   /* r_2 is an integer: r_2 < p 2^32 iff r_2 < ceil(p 2^32) */
+    H.B = B; H.der_state = ns.der; H.der_goal = ng.der;
+    H.x = out->d_x; H.xn = out->d_x_next; H.action = out->d_action; H.reward = out->d_reward; H.ok = out->d_goal_achieved; H.idx = idx;
+    HIP_TRY(e, pmg_launch_her(H, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {
@@ -1152,6 +1213,13 @@ int pmg_upload(pmg_env* e, void* d_dst, const void* h_src, uint64_t bytes)
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return PMG_OK;
+}
+int pmg_device_copy(pmg_env* e, void* d_dst, const void* d_src, uint64_t bytes)
+{
+    if (!e || !d_dst || !d_src) return PMG_E_INVALID;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, e->stream));
     return PMG_OK;
 }
 int pmg_download(pmg_env* e, void* h_dst, const void* d_src, uint64_t bytes)

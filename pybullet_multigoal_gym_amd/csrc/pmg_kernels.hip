@@ -502,13 +502,18 @@ __global__ void __launch_bounds__(256) pmg_k_norm_merge(const double* __restrict
  * from the packed rows).  mean / inv_std of the Ds + Dg columns sit in LDS.  The < 4 floats in front of the first 16-byte
  * boundary of d_out and behind the last full float4 are written as dwords by workgroup 0. */
 __device__ __forceinline__ unsigned int norm_bits(float f) { unsigned int u; __builtin_memcpy(&u, &f, 4); return u; }
+/* the one definition of a policy-input element (pmg_k_policy_input and pmg_k_her_rows: bit-equal by construction) */
+__device__ __forceinline__ float policy_norm(float v, float mean, float inv_std, float cin, float cout)
+{
+    v = fminf(fmaxf(v, -cin), cin);
+    v = (v - mean) * inv_std;
+    return fminf(fmaxf(v, -cout), cout);
+}
 __device__ __forceinline__ float policy_value(const float* __restrict__ s, long long ss, int Ds, const float* __restrict__ g, long long gs,
                                               const float* sm, const float* si, float cin, float cout, long long row, int col)
 {
-    float v = col < Ds ? nt::load(s + row * ss + col) : nt::load(g + row * gs + (col - Ds));
-    v = fminf(fmaxf(v, -cin), cin);
-    v = (v - sm[col]) * si[col];
-    return fminf(fmaxf(v, -cout), cout);
+    const float v = col < Ds ? nt::load(s + row * ss + col) : nt::load(g + row * gs + (col - Ds));
+    return policy_norm(v, sm[col], si[col], cin, cout);
 }
 __global__ void __launch_bounds__(256) pmg_k_policy_input(const float* __restrict__ s, long long ss, int Ds, const float* __restrict__ g,
                                                          long long gs, int Dg, const float* __restrict__ ders,
@@ -594,5 +599,153 @@ hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride,
     const unsigned grid = (unsigned)(want < 1 ? 1 : (want < 2048 ? want : 2048));
     hipLaunchKernelGGL(pmg_k_policy_input, dim3(grid), dim3(256), 0, s, d_state, state_stride, Ds, d_goal, goal_stride, Dg, der_state,
                        der_goal, clip_input, clip_output, head, n4, total, d_out);
+    return hipGetLastError();
+}
+
+/* HER minibatches from episode rows the caller keeps in device memory (pmg_her_sample_device).
+ * The draws (include/pmg.h): SplitMix64's finaliser over a counter, four 32-bit values per sample; multiply-shift
+ * maps them onto [0, E), [0, T) and (t, T], so no address depends on device data. */
+constexpr unsigned long long HER_GOLD = 0x9E3779B97F4A7C15ull;
+__host__ __device__ __forceinline__ unsigned long long her_mix(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+/* One thread per sample: the four draws -> e, t, f (idx; -1 = not relabelled), reward and flag of (achieved_goal(e, t + 1), g')
+ * from the 2 G goal floats, and the action row.  A lane per sample touches 64 different rows per wave-instruction -- the
+ * slow shape -- but only for these 2 G + A floats of a sample; the row sweep below carries the bulk.  The sum of squares
+ * runs in the order of pmg_k_reward. */
+__global__ void __launch_bounds__(256) pmg_k_her_draw(PmgHer H, unsigned long long key)
+{
+    for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < H.B; b += (long long)gridDim.x * 256) {
+        const unsigned long long z = key + (4ull * (unsigned long long)b + 1ull) * HER_GOLD;
+        const unsigned long long r0 = her_mix(z) >> 32, r1 = her_mix(z + HER_GOLD) >> 32, r2 = her_mix(z + 2ull * HER_GOLD) >> 32,
+                                 r3 = her_mix(z + 3ull * HER_GOLD) >> 32;
+        const int e = (int)((r0 * (unsigned long long)H.E) >> 32);
+        const int t = (int)((r1 * (unsigned long long)H.T) >> 32);
+        const int f = r2 < H.relabel_below ? t + 1 + (int)((r3 * (unsigned long long)(H.T - t)) >> 32) : -1;
+        if (H.idx) { int* ix = H.idx + 3 * b; ix[0] = e; ix[1] = t; ix[2] = f; }   /* re-read by the sweep: plain stores */
+        if (H.reward || H.ok) {
+            const float* row = H.rows + (long long)e * H.res + (long long)t * H.rts;
+            const float* ag = row + H.rts + H.ago;
+            const float* g = f >= 0 ? H.rows + (long long)e * H.res + (long long)f * H.rts + H.ago : row + H.dgo;
+            float s = 0.f;
+            for (int k = 0; k < H.G; k++) {
+                const float d = ag[k] - g[k];
+                s += d * d;
+            }
+            const float dist = sqrtf(s);
+            const bool na = dist > H.thr;
+            if (H.reward) nt::store(norm_bits(H.binary ? (na ? -1.f : -0.f) : -dist), (unsigned int*)(H.reward + b));
+            if (H.ok) H.ok[b] = na ? 0 : 1;
+        }
+        if (H.action) {
+            const float* a = H.act + (long long)e * H.aes + (long long)t * H.ats;
+            for (int k = 0; k < H.A; k++) nt::store(norm_bits(a[k]), (unsigned int*)(H.action + b * H.A + k));
+        }
+    }
+}
+/* The sweep of pmg_k_policy_input with indexed sources: x[B, Ds + Dg] = state(e, t) | g' and xn = state(e, t + 1) | g' are two
+ * flat streams; thread i writes float4 i of either (lane = consecutive 16 bytes of the output, and consecutive columns of
+ * ONE source row: a wave-instruction touches 256 / (4 W) + 1 rows, not 64) and keeps (sample, column) as counters.  mode 2
+ * fills both outputs in one launch -- they share the distance to their first 16-byte boundary -- and fetches g' once per
+ * sample; mode 0 / 1 fill x / xn alone.  Sources are plain loads (a replay table is read again), outputs non-temporal. */
+struct HerRowSrc { const float* s; const float* sn; const float* g; };
+__device__ __forceinline__ HerRowSrc her_row(const PmgHer& H, long long b)
+{
+    const int* ix = H.idx + 3 * b;
+    const int e = ix[0], t = ix[1], f = ix[2];
+    const float* r = H.rows + (long long)e * H.res + (long long)t * H.rts;
+    HerRowSrc o;
+    o.s = r + H.so;
+    o.sn = o.s + H.rts;
+    o.g = f >= 0 ? H.rows + (long long)e * H.res + (long long)f * H.rts + H.ago : r + H.dgo;
+    return o;
+}
+__device__ __forceinline__ void her_value(const PmgHer& H, const HerRowSrc& r, int col, const float* sm, const float* si, int mode,
+                                          float& x, float& xn)
+{
+    if (col >= H.Ds) {
+        float v = r.g[col - H.Ds];
+        if (!H.raw) v = policy_norm(v, sm[col], si[col], H.cin, H.cout);
+        x = xn = v;
+        return;
+    }
+    if (mode != 1) { x = r.s[col]; if (!H.raw) x = policy_norm(x, sm[col], si[col], H.cin, H.cout); }
+    if (mode != 0) { xn = r.sn[col]; if (!H.raw) xn = policy_norm(xn, sm[col], si[col], H.cin, H.cout); }
+}
+__global__ void __launch_bounds__(256) pmg_k_her_rows(PmgHer H, int mode, long long head, long long n4, long long total)
+{
+    __shared__ float sm[2 * PMG_NORM_MAX_D], si[2 * PMG_NORM_MAX_D];
+    const int W = H.Ds + H.G, t = (int)threadIdx.x;
+    if (!H.raw) {
+        for (int c = t; c < W; c += 256) {
+            sm[c] = c < H.Ds ? H.der_state[c] : H.der_goal[c - H.Ds];
+            si[c] = c < H.Ds ? H.der_state[2 * H.Ds + c] : H.der_goal[2 * H.G + (c - H.Ds)];
+        }
+        __syncthreads();
+    }
+    const long long sweep = (long long)gridDim.x * 256;        /* float4 per sweep of the grid */
+    long long i = (long long)blockIdx.x * 256 + t;
+    if (i < n4) {
+        const long long e = head + 4 * i;
+        long long row = e / W;
+        int col = (int)(e - row * W);
+        const long long drow = (4 * sweep) / W;
+        const int dcol = (int)(4 * sweep - drow * W);
+        float4* x4 = mode != 1 ? (float4*)(H.x + head) : nullptr;
+        float4* xn4 = mode != 0 ? (float4*)(H.xn + head) : nullptr;
+        for (; i < n4; i += sweep) {
+            float a[4], c[4];
+            long long rr = row;
+            int cc = col;
+            HerRowSrc src = her_row(H, rr);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                her_value(H, src, cc, sm, si, mode, a[k], c[k]);
+                if (++cc == W) { cc = 0; rr++; if (k < 3) src = her_row(H, rr); }   /* k < 3: element e + k + 1 < total, so rr < B */
+            }
+            if (mode != 1) nt::store4(make_float4(a[0], a[1], a[2], a[3]), x4 + i);
+            if (mode != 0) nt::store4(make_float4(c[0], c[1], c[2], c[3]), xn4 + i);
+            row += drow; col += dcol;
+            if (col >= W) { col -= W; row++; }
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long long body_end = head + 4 * n4;
+        const int extra = (int)(head + (total - body_end));     /* < 8 */
+        if (t < extra) {
+            const long long e = t < head ? (long long)t : body_end + (t - head);
+            const long long row = e / W;
+            float a = 0.f, c = 0.f;
+            her_value(H, her_row(H, row), (int)(e - row * W), sm, si, mode, a, c);
+            if (mode != 1) nt::store(norm_bits(a), (unsigned int*)(H.x + e));
+            if (mode != 0) nt::store(norm_bits(c), (unsigned int*)(H.xn + e));
+        }
+    }
+}
+static void launch_her_rows(const PmgHer& H, int mode, hipStream_t s)
+{
+    const float* out = mode == 1 ? H.xn : H.x;
+    const long long total = H.B * (H.Ds + H.G);
+    long long head = (long long)(((16 - ((size_t)out & 15)) & 15) / 4);
+    if (head > total) head = total;
+    const long long n4 = (total - head) / 4;
+    const long long want = (n4 + 255) / 256;
+    const unsigned grid = (unsigned)(want < 1 ? 1 : (want < 2048 ? want : 2048));   /* as pmg_launch_policy_input */
+    hipLaunchKernelGGL(pmg_k_her_rows, dim3(grid), dim3(256), 0, s, H, mode, head, n4, total);
+}
+hipError_t pmg_launch_her(const PmgHer& H, hipStream_t s)
+{
+    if (H.B <= 0) return hipSuccess;
+    const unsigned long long key = her_mix(H.seed ^ her_mix(H.counter + HER_GOLD));
+    const long long want = (H.B + 255) / 256;
+    hipLaunchKernelGGL(pmg_k_her_draw, dim3((unsigned)(want < (1 << 20) ? want : (1 << 20))), dim3(256), 0, s, H, key);
+    if (H.x && H.xn && (((size_t)H.x ^ (size_t)H.xn) & 15) == 0) launch_her_rows(H, 2, s);
+    else {
+        if (H.x) launch_her_rows(H, 0, s);
+        if (H.xn) launch_her_rows(H, 1, s);
+    }
     return hipGetLastError();
 }

@@ -29,4 +29,20 @@ hipError_t pmg_launch_norm_derive(int D, float eps, double* tot, float* der, hip
 hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride, int Ds, const float* d_goal, long long goal_stride,
                                    int Dg, long long B, const float* der_state, const float* der_goal, float clip_input,
                                    float clip_output, float* d_out, hipStream_t s);
+
+/* HER minibatches from caller-owned episode rows (pmg_her_sample_device): everything both kernels need, validated
+ * by the caller.  Row (e, t) of the table sits at rows + e * res + t * rts; so / ago / dgo = first column of the state kind,
+ * the achieved and the desired goal in a packed row.  idx is never null when x or xn is given. */
+struct PmgHer {
+    const float* rows; long long res, rts;
+    const float* act; long long aes, ats;
+    int E, T, A, Ds, G, so, ago, dgo;
+    int raw, binary;
+    float thr, cin, cout;
+    unsigned long long seed, counter, relabel_below;   /* relabelled iff r_2 < relabel_below = ceil(future_p * 2^32) */
+    long long B;
+    const float* der_state; const float* der_goal;     /* derived arrays of the two normalisers (unused when raw) */
+    float* x; float* xn; float* action; float* reward; unsigned char* ok; int* idx;
+};
+hipError_t pmg_launch_her(const PmgHer& H, hipStream_t s);
 #endif

@@ -277,6 +277,14 @@ class KukaVecEnv:
             self._normalizer = Normalizer(self)
         return self._normalizer
 
+    @property
+    def her(self):
+        """The HER minibatch sampler over episode rows of this env (her.HerSampler), created on first access."""
+        if getattr(self, '_her', None) is None:
+            from .her import HerSampler
+            self._her = HerSampler(self)
+        return self._her
+
     def close(self):
         if not self._closed:
             self.handle.close()
