@@ -93,6 +93,16 @@ struct Seeder { /* gym 0.17.3 seeding.np_random + numpy RandomState.seed(int lis
     }
 };
 
+/* A grow-only block of device scratch.  reserve() keeps a block that is large enough; otherwise it waits for the handle's stream
+ * (queued work may still read the old block), frees and allocates.  No destructor: pmg_destroy releases the blocks in its order. */
+struct Scratch {
+    void* p = nullptr;
+    size_t cap = 0;                   /* bytes */
+    int reserve(pmg_env* e, size_t bytes, const char* who, const char* what);
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+    float* f32() const { return (float*)p; }
+};
+
 }  // namespace
 
 struct pmg_env {
@@ -107,8 +117,9 @@ struct pmg_env {
     unsigned char* d_mask = nullptr;
     float* h_packed = nullptr;        /* pinned */
     float* h_actions = nullptr;       /* pinned */
-    float* d_rw_ag = nullptr; float* d_rw_dg = nullptr; float* d_rw_r = nullptr; unsigned char* d_rw_ok = nullptr;
-    long long rw_cap = 0;
+    /* staging of the synchronous host variants (pmg_compute_reward, pmg_norm_update, pmg_policy_input; never two at a time):
+     * two inputs, one output, one mask / flag block */
+    Scratch st_a, st_b, st_out, st_flag;
     hipEvent_t ev_a[EVENT_POOL], ev_b[EVENT_POOL];
     hipEvent_t cv_a[EVENT_POOL], cv_b[EVENT_POOL];   /* the same around every all-gather */
     int cv_n = 0;
@@ -139,10 +150,7 @@ struct pmg_env {
      * totals double[2 D + 1] | partials double[PMG_NORM_MAX_PARTS][2 D + 1] | derived float[3 D] */
     struct Norm { int D = 0; double* tot = nullptr; double* part = nullptr; float* der = nullptr; } norm[3];
     float norm_eps = 0.01f, norm_clip_in = 200.f, norm_clip_out = 5.f;
-    float* d_nm_a = nullptr; float* d_nm_b = nullptr; float* d_nm_out = nullptr; unsigned char* d_nm_mask = nullptr;   /* staging of the host variants */
-    long long nm_cap = 0;
-    int* d_her_idx = nullptr;         /* e, t, f of a pmg_her_sample_device batch whose caller passed no d_index */
-    long long her_cap = 0;            /* samples it holds */
+    Scratch her_idx;                  /* e, t, f of a pmg_her_sample_device batch whose caller passed no d_index: kept until a larger batch */
     char err[512] = "";
 };
 
@@ -165,6 +173,38 @@ int fail(pmg_env* e, int code, const char* fmt, ...)
         hipError_t rc_ = (call);                                                                     \
         if (rc_ != hipSuccess) return fail(e, PMG_E_DEVICE, "%s -> %s", #call, hipGetErrorString(rc_)); \
     } while (0)
+
+int Scratch::reserve(pmg_env* e, size_t bytes, const char* who, const char* what)
+{
+    if (bytes <= cap) return PMG_OK;
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    release();
+    if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return fail(e, PMG_E_NOMEM, "%s: no memory for %zu bytes of %s", who, bytes, what); }
+    cap = bytes;
+    return PMG_OK;
+}
+/* the staging blocks of the host variant `who`, in bytes */
+int stage(pmg_env* e, const char* who, size_t a, size_t b, size_t out, size_t flag)
+{
+    const char* what = "host staging";
+    if (int rc = e->st_a.reserve(e, a, who, what)) return rc;
+    if (int rc = e->st_b.reserve(e, b, who, what)) return rc;
+    if (int rc = e->st_out.reserve(e, out, who, what)) return rc;
+    return e->st_flag.reserve(e, flag, who, what);
+}
+/* the normaliser `which` of `who`'s caller, or its state normaliser (observation or policy_state); null with the error set */
+pmg_env::Norm* norm_of(pmg_env* e, int which, const char* who)
+{
+    if (which >= 0 && which <= 2) return &e->norm[which];
+    fail(e, PMG_E_INVALID, "%s: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", who, which);
+    return nullptr;
+}
+pmg_env::Norm* state_norm_of(pmg_env* e, int state_kind, const char* who)
+{
+    if (state_kind == PMG_NORM_OBSERVATION || state_kind == PMG_NORM_POLICY_STATE) return &e->norm[state_kind];
+    fail(e, PMG_E_INVALID, "%s: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", who, state_kind);
+    return nullptr;
+}
 
 int fill_dims(const pmg_config* c, pmg_dims* d, int* nb_out)
 {
@@ -491,12 +531,14 @@ void pmg_destroy(pmg_env* e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->comm_stream) (void)hipStreamSynchronize(e->comm_stream);   /* an overlapped all-gather in flight reads out2[] through e->comm */
     if (e->comm) ncclCommDestroy(e->comm);
-    (void)hipFree(e->P.hot); (void)hipFree(e->P.cold); (void)hipFree(e->P.goal); (void)hipFree(e->P.curr); (void)hipFree(e->P.blocks); (void)hipFree(e->P.rng); if (e->out2[1]) { (void)hipFree(e->out2[0]); (void)hipFree(e->out2[1]); } else (void)hipFree(e->P.out); (void)hipFree(e->P.sched); if (e->P.env_cycles) (void)hipFree(e->P.env_cycles); if (e->P.lpt_state) (void)hipFree(e->P.lpt_state);
+    (void)hipFree(e->P.hot); (void)hipFree(e->P.cold); (void)hipFree(e->P.goal);
+    (void)hipFree(e->P.curr); (void)hipFree(e->P.blocks); (void)hipFree(e->P.rng);
+    if (e->out2[1]) { (void)hipFree(e->out2[0]); (void)hipFree(e->out2[1]); }
+    else (void)hipFree(e->P.out);
+    (void)hipFree(e->P.sched); (void)hipFree(e->P.env_cycles); (void)hipFree(e->P.lpt_state);
     (void)hipFree(e->d_actions); (void)hipFree(e->d_mask);
-    (void)hipFree(e->d_rw_ag); (void)hipFree(e->d_rw_dg); (void)hipFree(e->d_rw_r); (void)hipFree(e->d_rw_ok);
     for (int w = 0; w < 3; w++) (void)hipFree(e->norm[w].tot);
-    (void)hipFree(e->d_nm_a); (void)hipFree(e->d_nm_b); (void)hipFree(e->d_nm_out); (void)hipFree(e->d_nm_mask);
-    (void)hipFree(e->d_her_idx);
+    for (Scratch* b : {&e->st_a, &e->st_b, &e->st_out, &e->st_flag, &e->her_idx}) b->release();
     if (e->h_packed) (void)hipHostFree(e->h_packed);
     if (e->h_actions) (void)hipHostFree(e->h_actions);
     for (int i = 0; i < EVENT_POOL; i++) { if (e->ev_a[i]) (void)hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) (void)hipEventDestroy(e->ev_b[i]); }
@@ -680,22 +722,14 @@ int pmg_compute_reward(pmg_env* e, const float* ag, const float* dg, int64_t bat
     if (!e || !ag || !dg || batch < 0) return PMG_E_INVALID;
     if (batch == 0) return PMG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    int G = e->dims.goal_dim;
-    if (batch > e->rw_cap) {
-        (void)hipFree(e->d_rw_ag); (void)hipFree(e->d_rw_dg); (void)hipFree(e->d_rw_r); (void)hipFree(e->d_rw_ok);
-        e->d_rw_ag = e->d_rw_dg = e->d_rw_r = nullptr; e->d_rw_ok = nullptr; e->rw_cap = 0;
-        HIP_TRY(e, hipMalloc((void**)&e->d_rw_ag, (size_t)batch * G * sizeof(float)));
-        HIP_TRY(e, hipMalloc((void**)&e->d_rw_dg, (size_t)batch * G * sizeof(float)));
-        HIP_TRY(e, hipMalloc((void**)&e->d_rw_r, (size_t)batch * sizeof(float)));
-        HIP_TRY(e, hipMalloc((void**)&e->d_rw_ok, (size_t)batch));
-        e->rw_cap = batch;
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->d_rw_ag, ag, (size_t)batch * G * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_rw_dg, dg, (size_t)batch * G * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    int rc = pmg_compute_reward_device(e, e->d_rw_ag, e->d_rw_dg, batch, e->d_rw_r, e->d_rw_ok);
+    const size_t goals = (size_t)batch * e->dims.goal_dim * sizeof(float);
+    if (int rc = stage(e, "pmg_compute_reward", goals, goals, (size_t)batch * sizeof(float), (size_t)batch)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->st_a.p, ag, goals, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->st_b.p, dg, goals, hipMemcpyHostToDevice, e->stream));
+    int rc = pmg_compute_reward_device(e, e->st_a.f32(), e->st_b.f32(), batch, e->st_out.f32(), (uint8_t*)e->st_flag.p);
     if (rc != PMG_OK) return rc;
-    if (r) HIP_TRY(e, hipMemcpyAsync(r, e->d_rw_r, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    if (ok) HIP_TRY(e, hipMemcpyAsync(ok, e->d_rw_ok, (size_t)batch, hipMemcpyDeviceToHost, e->stream));
+    if (r) HIP_TRY(e, hipMemcpyAsync(r, e->st_out.p, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (ok) HIP_TRY(e, hipMemcpyAsync(ok, e->st_flag.p, (size_t)batch, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return PMG_OK;
 }
@@ -704,20 +738,6 @@ int pmg_compute_reward(pmg_env* e, const float* ag, const float* dg, int64_t bat
 static int norm_derive_all(pmg_env* e)
 {
     for (int w = 0; w < 3; w++) HIP_TRY(e, pmg_launch_norm_derive(e->norm[w].D, e->norm_eps, e->norm[w].tot, e->norm[w].der, e->stream));
-    return PMG_OK;
-}
-/* staging of the host variants: two input arrays, one output array of `floats` floats each and `floats` mask bytes */
-static int norm_stage(pmg_env* e, long long floats)
-{
-    if (floats <= e->nm_cap) return PMG_OK;
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    (void)hipFree(e->d_nm_a); (void)hipFree(e->d_nm_b); (void)hipFree(e->d_nm_out); (void)hipFree(e->d_nm_mask);
-    e->d_nm_a = e->d_nm_b = e->d_nm_out = nullptr; e->d_nm_mask = nullptr; e->nm_cap = 0;
-    HIP_TRY(e, hipMalloc((void**)&e->d_nm_a, (size_t)floats * sizeof(float)));
-    HIP_TRY(e, hipMalloc((void**)&e->d_nm_b, (size_t)floats * sizeof(float)));
-    HIP_TRY(e, hipMalloc((void**)&e->d_nm_out, 2 * (size_t)floats * sizeof(float)));
-    HIP_TRY(e, hipMalloc((void**)&e->d_nm_mask, (size_t)floats));
-    e->nm_cap = floats;
     return PMG_OK;
 }
 
@@ -741,11 +761,11 @@ static int norm_update_rows(pmg_env* e, int which, const float* d_rows, int64_t 
 int pmg_norm_update_device(pmg_env* e, int which, const float* d_rows, int64_t row_stride, int64_t batch, const uint8_t* d_mask)
 {
     if (!e) return PMG_E_INVALID;
-    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    const pmg_env::Norm* nm = norm_of(e, which, "pmg_norm_update_device"); if (!nm) return PMG_E_INVALID;
     if (!d_rows) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: d_rows is null");
     if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: batch %lld is negative", (long long)batch);
-    if (row_stride < e->norm[which].D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: row_stride %lld is smaller than the width %d", (long long)row_stride, e->norm[which].D);
-    if (e->norm[which].D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: width %d beyond %d", e->norm[which].D, PMG_NORM_MAX_D);
+    if (row_stride < nm->D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: row_stride %lld is smaller than the width %d", (long long)row_stride, nm->D);
+    if (nm->D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_norm_update_device: width %d beyond %d", nm->D, PMG_NORM_MAX_D);
     if (batch == 0) return PMG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     return norm_update_rows(e, which, d_rows, row_stride, batch, 0, d_mask);
@@ -754,16 +774,16 @@ int pmg_norm_update_device(pmg_env* e, int which, const float* d_rows, int64_t r
 int pmg_norm_update(pmg_env* e, int which, const float* rows, int64_t batch, const uint8_t* mask)
 {
     if (!e) return PMG_E_INVALID;
-    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_update: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    const pmg_env::Norm* nm = norm_of(e, which, "pmg_norm_update"); if (!nm) return PMG_E_INVALID;
     if (!rows) return fail(e, PMG_E_INVALID, "pmg_norm_update: rows is null");
     if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_norm_update: batch %lld is negative", (long long)batch);
     if (batch == 0) return PMG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    const int D = e->norm[which].D;
-    if (int rc = norm_stage(e, batch * D)) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_nm_a, rows, (size_t)batch * D * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    if (mask) HIP_TRY(e, hipMemcpyAsync(e->d_nm_mask, mask, (size_t)batch, hipMemcpyHostToDevice, e->stream));
-    int rc = pmg_norm_update_device(e, which, e->d_nm_a, D, batch, mask ? e->d_nm_mask : nullptr);
+    const size_t bytes = (size_t)batch * nm->D * sizeof(float);
+    if (int rc = stage(e, "pmg_norm_update", bytes, 0, 0, mask ? (size_t)batch : 0)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->st_a.p, rows, bytes, hipMemcpyHostToDevice, e->stream));
+    if (mask) HIP_TRY(e, hipMemcpyAsync(e->st_flag.p, mask, (size_t)batch, hipMemcpyHostToDevice, e->stream));
+    int rc = pmg_norm_update_device(e, which, e->st_a.f32(), nm->D, batch, mask ? (const uint8_t*)e->st_flag.p : nullptr);
     if (rc != PMG_OK) return rc;
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return PMG_OK;
@@ -785,9 +805,9 @@ int pmg_norm_update_env_device(pmg_env* e, const uint8_t* d_mask)
 int pmg_norm_read(pmg_env* e, int which, double* sum, double* sumsq, double* count, float* mean, float* std_, float* inv_std)
 {
     if (!e) return PMG_E_INVALID;
-    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_read: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    const pmg_env::Norm* found = norm_of(e, which, "pmg_norm_read"); if (!found) return PMG_E_INVALID;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    const pmg_env::Norm& nm = e->norm[which];
+    const pmg_env::Norm& nm = *found;
     const size_t D = (size_t)nm.D;
     std::vector<double> tot(2 * D + 1);
     std::vector<float> der(3 * D);
@@ -806,11 +826,11 @@ int pmg_norm_read(pmg_env* e, int which, double* sum, double* sumsq, double* cou
 int pmg_norm_write(pmg_env* e, int which, const double* sum, const double* sumsq, double count)
 {
     if (!e) return PMG_E_INVALID;
-    if (which < 0 || which > 2) return fail(e, PMG_E_INVALID, "pmg_norm_write: normaliser %d is none of PMG_NORM_OBSERVATION / _POLICY_STATE / _GOAL", which);
+    pmg_env::Norm* found = norm_of(e, which, "pmg_norm_write"); if (!found) return PMG_E_INVALID;
     if (!(count >= 0.0) || std::isinf(count)) return fail(e, PMG_E_INVALID, "pmg_norm_write: count %g must be finite and >= 0", count);
     if ((!sum || !sumsq) && count != 0.0) return fail(e, PMG_E_INVALID, "pmg_norm_write: null totals are zeros and need count == 0");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    pmg_env::Norm& nm = e->norm[which];
+    pmg_env::Norm& nm = *found;
     const size_t D = (size_t)nm.D;
     std::vector<double> tot(2 * D + 1, 0.0);
     if (sum) memcpy(tot.data(), sum, D * sizeof(double));
@@ -826,12 +846,11 @@ int pmg_policy_input_device(pmg_env* e, int state_kind, const float* d_state, in
                             int64_t goal_stride, int64_t batch, float* d_out)
 {
     if (!e) return PMG_E_INVALID;
-    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
-        return fail(e, PMG_E_INVALID, "pmg_policy_input_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    const pmg_env::Norm* found = state_norm_of(e, state_kind, "pmg_policy_input_device"); if (!found) return PMG_E_INVALID;
     if (!d_state || !d_goal || !d_out) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: null pointer");
     if (((size_t)d_out & 3) != 0) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: d_out is not aligned to a float");
     if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_policy_input_device: batch %lld is negative", (long long)batch);
-    const pmg_env::Norm& ns = e->norm[state_kind];
+    const pmg_env::Norm& ns = *found;
     const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
     if (state_stride < ns.D || goal_stride < ng.D)
         return fail(e, PMG_E_INVALID, "pmg_policy_input_device: strides %lld / %lld are smaller than the widths %d / %d", (long long)state_stride, (long long)goal_stride, ns.D, ng.D);
@@ -845,19 +864,19 @@ int pmg_policy_input_device(pmg_env* e, int state_kind, const float* d_state, in
 int pmg_policy_input(pmg_env* e, int state_kind, const float* state, const float* goal, int64_t batch, float* out)
 {
     if (!e) return PMG_E_INVALID;
-    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
-        return fail(e, PMG_E_INVALID, "pmg_policy_input: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    const pmg_env::Norm* ns = state_norm_of(e, state_kind, "pmg_policy_input"); if (!ns) return PMG_E_INVALID;
     if (!state || !goal || !out) return fail(e, PMG_E_INVALID, "pmg_policy_input: null pointer");
     if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_policy_input: batch %lld is negative", (long long)batch);
     if (batch == 0) return PMG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    const int Ds = e->norm[state_kind].D, Dg = e->norm[PMG_NORM_GOAL].D;
-    if (int rc = norm_stage(e, batch * (Ds > Dg ? Ds : Dg))) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->d_nm_a, state, (size_t)batch * Ds * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(e, hipMemcpyAsync(e->d_nm_b, goal, (size_t)batch * Dg * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    int rc = pmg_policy_input_device(e, state_kind, e->d_nm_a, Ds, e->d_nm_b, Dg, batch, e->d_nm_out);
+    const int Ds = ns->D, Dg = e->norm[PMG_NORM_GOAL].D;
+    const size_t sb = (size_t)batch * Ds * sizeof(float), gb = (size_t)batch * Dg * sizeof(float);
+    if (int rc = stage(e, "pmg_policy_input", sb, gb, sb + gb, 0)) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->st_a.p, state, sb, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->st_b.p, goal, gb, hipMemcpyHostToDevice, e->stream));
+    int rc = pmg_policy_input_device(e, state_kind, e->st_a.f32(), Ds, e->st_b.f32(), Dg, batch, e->st_out.f32());
     if (rc != PMG_OK) return rc;
-    HIP_TRY(e, hipMemcpyAsync(out, e->d_nm_out, (size_t)batch * (Ds + Dg) * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(out, e->st_out.p, sb + gb, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
     return PMG_OK;
 }
@@ -865,8 +884,7 @@ int pmg_policy_input(pmg_env* e, int state_kind, const float* state, const float
 int pmg_policy_input_env_device(pmg_env* e, int state_kind, float* d_out)
 {
     if (!e) return PMG_E_INVALID;
-    if (state_kind != PMG_NORM_OBSERVATION && state_kind != PMG_NORM_POLICY_STATE)
-        return fail(e, PMG_E_INVALID, "pmg_policy_input_env_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", state_kind);
+    if (!state_norm_of(e, state_kind, "pmg_policy_input_env_device")) return PMG_E_INVALID;
     if (!d_out) return fail(e, PMG_E_INVALID, "pmg_policy_input_env_device: d_out is null");
     if (!e->ever_reset) return fail(e, PMG_E_STATE, "pmg_policy_input_env_device: reset() must be called (for all envs) first");
     const pmg_dims& d = e->dims;
@@ -896,26 +914,20 @@ int pmg_her_sample_device(pmg_env* e, const pmg_her_source* src, const pmg_her_b
     if (out->d_action && !src->d_actions) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: d_action needs d_actions");
     if (src->d_actions && (!her_stride_ok(src->action_episode_stride, E, d.action_dim) || !her_stride_ok(src->action_time_stride, T, d.action_dim)))
         return fail(e, PMG_E_INVALID, "pmg_her_sample_device: action strides %lld / %lld are smaller than action_dim %d", (long long)src->action_episode_stride, (long long)src->action_time_stride, d.action_dim);
-    if (out->state_kind != PMG_NORM_OBSERVATION && out->state_kind != PMG_NORM_POLICY_STATE)
-        return fail(e, PMG_E_INVALID, "pmg_her_sample_device: state_kind %d is neither PMG_NORM_OBSERVATION nor PMG_NORM_POLICY_STATE", out->state_kind);
+    const pmg_env::Norm* found = state_norm_of(e, out->state_kind, "pmg_her_sample_device"); if (!found) return PMG_E_INVALID;
     if (!(out->future_p >= 0.f && out->future_p <= 1.f)) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: future_p %g is outside [0, 1]", (double)out->future_p);
     if ((((size_t)src->d_rows | (size_t)src->d_actions | (size_t)out->d_x | (size_t)out->d_x_next | (size_t)out->d_action | (size_t)out->d_reward | (size_t)out->d_index) & 3) != 0)
         return fail(e, PMG_E_INVALID, "pmg_her_sample_device: a float / int32 pointer is not aligned to 4 bytes");
-    const pmg_env::Norm& ns = e->norm[out->state_kind];
+    const pmg_env::Norm& ns = *found;
     const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
     if (ns.D > PMG_NORM_MAX_D || ng.D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "pmg_her_sample_device: width beyond %d", PMG_NORM_MAX_D);
     if (B == 0 || !(out->d_x || out->d_x_next || out->d_action || out->d_reward || out->d_goal_achieved || out->d_index)) return PMG_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     int* idx = out->d_index;
     if (!idx && (out->d_x || out->d_x_next)) {
-        if (B > e->her_cap) {   /* sized at the first call; a larger batch later waits for the stream once */
-            HIP_TRY(e, hipStreamSynchronize(e->stream));
-            (void)hipFree(e->d_her_idx);
-            e->d_her_idx = nullptr; e->her_cap = 0;
-            if (hipMalloc((void**)&e->d_her_idx, (size_t)B * 3 * sizeof(int)) != hipSuccess) return fail(e, PMG_E_NOMEM, "pmg_her_sample_device: no memory for %lld index rows", (long long)B);
-            e->her_cap = B;
-        }
-        idx = e->d_her_idx;
+        /* sized at the first call; a larger batch later waits for the stream once */
+        if (int rc = e->her_idx.reserve(e, (size_t)B * 3 * sizeof(int), "pmg_her_sample_device", "index rows")) return rc;
+        idx = (int*)e->her_idx.p;
     }
     PmgHer H;
     H.rows = src->d_rows; H.res = src->row_episode_stride; H.rts = src->row_time_stride;

@@ -1,0 +1,437 @@
+/* pmg_learner_body.inc -- the learner-side kernels and their launchers (included by pmg_kernels.hip): rewards of [B, G] batches,
+ * the running normaliser, policy-input rows and HER minibatches (DESIGN.md 3.6-3.8).  None of them touches EnvParams.  What two
+ * kernels share has ONE definition, so that they agree bit for bit by construction: reward_of, sq_dist, policy_norm, flat_sweep. */
+/* distance, threshold, binary -> reward value and flag: the one definition (all three reward kernels and pmg_k_her_draw) */
+__device__ __forceinline__ float reward_of(float d, float thr, int binary, unsigned char& ok)
+{
+    const bool na = d > thr;
+    ok = na ? 0 : 1;
+    return binary ? (na ? -1.f : -0.f) : -d;
+}
+/* the dword sum of squares of item i of two [*, G] arrays, columns in ascending order (pmg_k_reward and pmg_k_her_draw) */
+__device__ __forceinline__ float sq_dist(const float* __restrict__ a, const float* __restrict__ b, long long i, int G)
+{
+    float s = 0.f;
+    for (int g = 0; g < G; g++) {
+        const float e = a[i * G + g] - b[i * G + g];
+        s += e * e;
+    }
+    return s;
+}
+
+/* _compute_reward on [B, G] batches (HER relabelling): kuka_single_step_base_env.py:237-244.
+ * HBM-bound: 2*G*4 bytes in, 5 bytes out per item, each touched once -- so every access is non-temporal (streams past
+ * the caches).  G == 3 (every single-object task): a workgroup owns 256 quads of 4 items = 3 x 256 float4 per array,
+ * read as three fully coalesced float4 sweeps (lane = consecutive 16 bytes) into LDS; thread t then takes the three
+ * float4 of ITS quad from LDS (stride 3: conflict-free), computes four rewards and stores one float4 of rewards and one
+ * dword of flags, contiguously.  Measured (tools/reward_variants.hip, 64 Mi pairs): 6.1-6.3 TB/s = the float4-copy
+ * ceiling of the part (MI355X_MICROARCH.md: 6.29), against 5.0-5.6 for the thread-owns-three-strided-float4 version
+ * of rounds 1-2 (with or without non-temporal stores, one or two quads in flight). */
+__global__ void __launch_bounds__(256) pmg_k_reward3(const float4* __restrict__ ag, const float4* __restrict__ dg, long long quads,
+                                                    float thr, int binary, float4* __restrict__ reward,
+                                                    unsigned int* __restrict__ ok)
+{
+    __shared__ float4 sa[3 * 256], sd[3 * 256];
+    const int t = (int)threadIdx.x;
+    for (long long base = (long long)blockIdx.x * 256; base < quads; base += (long long)gridDim.x * 256) {
+        const long long n = quads - base < 256 ? quads - base : 256;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const long long w = k * 256 + t;
+            if (w < 3 * n) { sa[w] = nt::load4(&ag[3 * base + w]); sd[w] = nt::load4(&dg[3 * base + w]); }
+        }
+        __syncthreads();
+        if (t < n) {
+            const float4 a0 = sa[3 * t], a1 = sa[3 * t + 1], a2 = sa[3 * t + 2], d0 = sd[3 * t], d1 = sd[3 * t + 1], d2 = sd[3 * t + 2];
+            float e[12] = {a0.x - d0.x, a0.y - d0.y, a0.z - d0.z, a0.w - d0.w, a1.x - d1.x, a1.y - d1.y,
+                           a1.z - d1.z, a1.w - d1.w, a2.x - d2.x, a2.y - d2.y, a2.z - d2.z, a2.w - d2.w};
+            float r[4];
+            unsigned int flags = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                unsigned char good;
+                r[i] = reward_of(sqrtf(e[3 * i] * e[3 * i] + e[3 * i + 1] * e[3 * i + 1] + e[3 * i + 2] * e[3 * i + 2]), thr, binary, good);
+                flags |= (unsigned int)good << (8 * i);
+            }
+            if (reward) nt::store4(make_float4(r[0], r[1], r[2], r[3]), &reward[base + t]);
+            if (ok) nt::store(flags, &ok[base + t]);
+        }
+        __syncthreads();
+    }
+}
+/* multi-block goals (G = 3 * num_block, up to 19 with the gripper tail): a workgroup owns 256 consecutive items = one
+ * contiguous span of 256 * G floats = 64 * G float4 per array WHATEVER G is.  Its threads read that span flat as float4
+ * (lane = consecutive 16 bytes: fully coalesced, non-temporal), every load of a thread in flight before the first use,
+ * and leave the four squared differences of each float4 in LDS; thread t then adds the G squares of item t (stride G) and
+ * stores one reward and one flag, contiguously.  One workgroup per 256 items, no grid-stride below 2^20 workgroups.
+ * Measured (tools/reward_flat_variants.hip, 16 Mi pairs, G = 7 / 9 / 12 / 13 / 16 / 19): 6.0-6.1 TB/s at every G against
+ * 5.2-5.6 for round 3's kernel (dword loads when G % 4 != 0, loads issued one per loop trip, 8192 workgroups striding);
+ * partial sums per float4 when G % 4 == 0 (less LDS traffic) measured 5.9, flags packed into dwords the same as bytes. */
+__global__ void __launch_bounds__(256) pmg_k_reward_flat(const float* __restrict__ ag, const float* __restrict__ dg, long long B, int G,
+                                                        float thr, int binary, float* __restrict__ reward,
+                                                        unsigned char* __restrict__ ok)
+{
+    constexpr int MAXQ = 5;                                    /* float4 per thread per array: G <= 20 */
+    __shared__ float4 sq[MAXQ * 256];
+    const int t = (int)threadIdx.x;
+    const int q4 = G * 64;                                     /* float4 per array of a full workgroup */
+    for (long long base = (long long)blockIdx.x * 256; base + 256 <= B; base += (long long)gridDim.x * 256) {
+        const float4* a = (const float4*)(ag + base * G);
+        const float4* d = (const float4*)(dg + base * G);
+        float4 x[MAXQ], y[MAXQ];
+#pragma unroll
+        for (int k = 0; k < MAXQ; k++) {
+            const int w = t + 256 * k;
+            if (w < q4) { x[k] = nt::load4(a + w); y[k] = nt::load4(d + w); }
+        }
+#pragma unroll
+        for (int k = 0; k < MAXQ; k++) {
+            const int w = t + 256 * k;
+            if (w < q4) {
+                const float e0 = x[k].x - y[k].x, e1 = x[k].y - y[k].y, e2 = x[k].z - y[k].z, e3 = x[k].w - y[k].w;
+                sq[w] = make_float4(e0 * e0, e1 * e1, e2 * e2, e3 * e3);
+            }
+        }
+        __syncthreads();
+        const float* part = (const float*)sq + t * G;
+        float s = 0.f;
+        for (int k = 0; k < G; k++) s += part[k];
+        unsigned char good;
+        const float r = reward_of(sqrtf(s), thr, binary, good);
+        if (reward) reward[base + t] = r;
+        if (ok) ok[base + t] = good;
+        __syncthreads();
+    }
+}
+/* any G, and the < 4 tail items of the G == 3 path */
+__global__ void __launch_bounds__(256) pmg_k_reward(const float* __restrict__ ag, const float* __restrict__ dg, long long first,
+                                                   long long B, int G, float thr, int binary, float* __restrict__ reward,
+                                                   unsigned char* __restrict__ ok)
+{
+    long long i = first + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    unsigned char good;
+    const float r = reward_of(sqrtf(sq_dist(ag, dg, i, G)), thr, binary, good);
+    if (reward) reward[i] = r;
+    if (ok) ok[i] = good;
+}
+hipError_t pmg_launch_reward(const float* ag, const float* dg, long long B, int G, float thr, int binary, float* reward,
+                             unsigned char* ok, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    long long first = 0;
+    bool aligned = ((((size_t)ag | (size_t)dg | (size_t)reward) & 15) == 0) && (((size_t)ok & 3) == 0);
+    if (G == 3 && aligned && B >= 4) {
+        long long quads = B / 4;
+        long long want = (quads + 255) / 256;
+        unsigned grid = (unsigned)(want < 65536 ? want : 65536); /* a workgroup per 256 quads (measured best), grid-stride beyond 64 Mi items */
+        hipLaunchKernelGGL(pmg_k_reward3, dim3(grid), dim3(256), 0, s, (const float4*)ag, (const float4*)dg, quads, thr, binary,
+                           (float4*)reward, (unsigned int*)ok);
+        first = quads * 4;
+    }
+    static const int generic_only = getenv("PMG_REWARD_GENERIC") ? atoi(getenv("PMG_REWARD_GENERIC")) : 0;   /* (counter calibration: the dword kernel) */
+    if (G > 3 && G <= 20 && B >= 256 && ((((size_t)ag | (size_t)dg) & 15) == 0) && !generic_only) {
+        long long want = B / 256;                                /* full workgroups; the < 256 tail items go to pmg_k_reward */
+        unsigned grid = (unsigned)(want < (1 << 20) ? want : (1 << 20));
+        hipLaunchKernelGGL(pmg_k_reward_flat, dim3(grid), dim3(256), 0, s, ag, dg, B, G, thr, binary, reward, ok);
+        first = want * 256;
+    }
+    if (first < B) {
+        unsigned grid = (unsigned)((B - first + 255) / 256);
+        hipLaunchKernelGGL(pmg_k_reward, dim3(grid), dim3(256), 0, s, ag, dg, first, B, G, thr, binary, reward, ok);
+    }
+    return hipGetLastError();
+}
+
+/* Running normaliser of HER learners (DESIGN.md 3.7): per column S = sum x', Q = sum x'^2 of the input-clipped rows and the row
+ * count n, in double.  The order of every addition is a function of (B, D, row0) alone -- no atomics: workgroup w owns the
+ * rows of chunk w (chunks are cut at multiples of `chunk` in GLOBAL row indices, `lead` = row0 % chunk), thread (j, c) adds
+ * rows j, j + J, ... of column c in ascending order (W = the power of two >= D columns side by side, J = 256 / W rows),
+ * an LDS tree folds the J row slots, and pmg_k_norm_merge adds the partial rows in index order.  Rows are read in place:
+ * any row stride, any alignment (dword loads; the goal columns of a reach packed row start at float 9). */
+__global__ void __launch_bounds__(256) pmg_k_norm_partial(const float* __restrict__ rows, long long stride, long long B, int D, int W,
+                                                         long long chunk, long long lead, const unsigned char* __restrict__ mask,
+                                                         float clip, double* __restrict__ part)
+{
+    __shared__ double ss[256], sq[256], sc[256];
+    const int t = (int)threadIdx.x, c = t & (W - 1), j = t / W, J = 256 / W;
+    long long r0 = (long long)blockIdx.x * chunk - lead, r1 = r0 + chunk;
+    if (r0 < 0) r0 = 0;
+    if (r1 > B) r1 = B;
+    double s = 0.0, q = 0.0, n = 0.0;
+    if (c < D)
+        for (long long r = r0 + j; r < r1; r += J) {
+            if (mask != nullptr && mask[r] == 0) continue;
+            const float x = fminf(fmaxf(nt::load(rows + r * stride + c), -clip), clip);
+            const double d = (double)x;
+            s += d; q += d * d; n += 1.0;
+        }
+    ss[t] = s; sq[t] = q; sc[t] = n;
+    __syncthreads();
+    for (int h = J >> 1; h >= 1; h >>= 1) {
+        if (j < h) { ss[t] += ss[t + h * W]; sq[t] += sq[t + h * W]; sc[t] += sc[t + h * W]; }
+        __syncthreads();
+    }
+    if (j == 0 && c < D) {
+        double* p = part + (size_t)blockIdx.x * (2 * D + 1);
+        p[c] = ss[t]; p[D + c] = sq[t];
+        if (c == 0) p[2 * D] = sc[t];
+    }
+}
+/* one workgroup: partial rows added in index order, then to the totals; mean | std | inv_std re-derived from the totals
+ * (nparts == 0: only that -- pmg_norm_configure, pmg_norm_write) */
+__global__ void __launch_bounds__(256) pmg_k_norm_merge(const double* __restrict__ part, int nparts, int D, double* __restrict__ tot,
+                                                       float* __restrict__ der, float eps)
+{
+    __shared__ double sn;
+    const int t = (int)threadIdx.x, P = 2 * D + 1;
+    if (t == 0) {
+        double a = 0.0;
+        for (int p = 0; p < nparts; p++) a += part[(size_t)p * P + 2 * D];
+        sn = tot[2 * D] + a;
+        tot[2 * D] = sn;
+    }
+    __syncthreads();
+    const double n = sn, e2 = (double)eps * (double)eps;
+    for (int c = t; c < D; c += 256) {
+        double s = 0.0, q = 0.0;
+        for (int p = 0; p < nparts; p++) { s += part[(size_t)p * P + c]; q += part[(size_t)p * P + D + c]; }
+        s = tot[c] + s; q = tot[D + c] + q;
+        tot[c] = s; tot[D + c] = q;
+        float mean = 0.f, sd = 1.f, inv = 1.f;
+        if (n > 0.0) {
+            const double m = s / n;
+            double var = q / n - m * m;
+            if (!(var > e2)) var = e2;
+            const double r = sqrt(var);
+            mean = (float)m; sd = (float)r; inv = (float)(1.0 / r);
+        }
+        der[c] = mean; der[D + c] = sd; der[2 * D + c] = inv;
+    }
+}
+static long long norm_chunk(long long B)
+{
+    /* at most PMG_NORM_MAX_PARTS - 2 chunks of a multiple of PMG_NORM_CHUNK_MIN rows (+ 1 for a leading partial chunk) */
+    const long long per = (long long)PMG_NORM_CHUNK_MIN * (PMG_NORM_MAX_PARTS - 2);
+    return PMG_NORM_CHUNK_MIN * ((B + per - 1) / per);
+}
+hipError_t pmg_launch_norm_derive(int D, float eps, double* tot, float* der, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, (const double*)nullptr, 0, D, tot, der, eps);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_norm_update(const float* d_rows, long long row_stride, long long B, int D, long long row0,
+                                  const unsigned char* d_mask, float clip_input, float eps, double* part, double* tot,
+                                  float* der, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    int W = 1;
+    while (W < D) W <<= 1;
+    const long long chunk = norm_chunk(B), lead = row0 % chunk;
+    const int nparts = (int)((lead + B + chunk - 1) / chunk);   /* <= PMG_NORM_MAX_PARTS */
+    hipLaunchKernelGGL(pmg_k_norm_partial, dim3(nparts), dim3(256), 0, s, d_rows, row_stride, B, D, W, chunk, lead, d_mask, clip_input, part);
+    hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, (const double*)part, nparts, D, tot, der, eps);
+    return hipGetLastError();
+}
+
+/* Policy-input rows out[B, Ds + Dg] = clip((clip(v, clip_in) - mean) * inv_std, clip_out) of state | goal rows.  HBM-bound like the
+ * reward kernels above: 4 bytes in and 4 bytes out per element, each touched once.  flat_sweep: an output is ONE flat stream of
+ * B (Ds + Dg) floats: thread i of the sweep writes its float4 i (lane = consecutive 16 bytes, whatever the row width; non-temporal)
+ * and gathers the four inputs by (row, column), which it keeps as counters: one 64-bit division per thread, none per element.
+ * Inputs are read as dwords: rows come with any stride and alignment (in place from the packed rows).  mean / inv_std of the
+ * Ds + Dg columns sit in LDS.  The < 4 floats in front of the first 16-byte boundary of the output and behind the last full
+ * float4 are written as dwords by workgroup 0.  The sweep is written once, over a ROW SOURCE Src of N = 1 or 2 output streams that
+ * share their distance to a 16-byte boundary: row(r) = the source pointers of output row r; fetch(row, col, f, v): v[n] =
+ * f(element col of that row, col) for every live stream n; live(n), out(n) = whether and where stream n is written. */
+__device__ __forceinline__ unsigned int norm_bits(float f) { unsigned int u; __builtin_memcpy(&u, &f, 4); return u; }
+/* the one definition of a policy-input element (pmg_k_policy_input and pmg_k_her_rows: bit-equal by construction) */
+__device__ __forceinline__ float policy_norm(float v, float mean, float inv_std, float cin, float cout)
+{
+    v = fminf(fmaxf(v, -cin), cin);
+    v = (v - mean) * inv_std;
+    return fminf(fmaxf(v, -cout), cout);
+}
+/* what a row source applies to every element it fetches: the policy-input element of column col, or (raw) the value itself */
+struct PolicyCols {
+    const float* mean; const float* inv_std; float cin, cout; bool raw;
+    __device__ __forceinline__ float operator()(float v, int col) const { return raw ? v : policy_norm(v, mean[col], inv_std[col], cin, cout); }
+};
+/* the flat stream of B rows of W floats at `out`: head floats (< 4) up to the first 16-byte boundary, n4 float4, total floats; its grid */
+struct FlatSpan { long long head, n4, total; unsigned grid; };
+static FlatSpan flat_span(const float* out, long long B, int W)
+{
+    const long long total = B * W, lead = (long long)(((16 - ((size_t)out & 15)) & 15) / 4), head = lead < total ? lead : total;
+    const long long n4 = (total - head) / 4, want = (n4 + 255) / 256;
+    /* 2048 workgroups of four wavefronts fill the 256 compute units (8 wavefronts per SIMD); larger batches stride */
+    return {head, n4, total, (unsigned)(want < 1 ? 1 : (want < 2048 ? want : 2048))};
+}
+template <class Src>
+__device__ __forceinline__ void flat_sweep(const Src& S, const float* __restrict__ ders, int Ds, const float* __restrict__ derg, int Dg,
+                                           bool raw, float cin, float cout, const FlatSpan& F)
+{
+    constexpr int N = Src::N;
+    __shared__ float sm[2 * PMG_NORM_MAX_D], si[2 * PMG_NORM_MAX_D];
+    const int W = Ds + Dg, t = (int)threadIdx.x;
+    if (!raw) {
+        for (int c = t; c < W; c += 256) {
+            sm[c] = c < Ds ? ders[c] : derg[c - Ds];
+            si[c] = c < Ds ? ders[2 * Ds + c] : derg[2 * Dg + (c - Ds)];
+        }
+        __syncthreads();
+    }
+    const PolicyCols f = {sm, si, cin, cout, raw};
+    const long long head = F.head, n4 = F.n4;
+    const long long sweep = (long long)gridDim.x * 256;        /* float4 per sweep of the grid */
+    long long i = (long long)blockIdx.x * 256 + t;
+    if (i < n4) {
+        const long long e = head + 4 * i;
+        long long row = e / W;
+        int col = (int)(e - row * W);
+        const long long drow = (4 * sweep) / W;
+        const int dcol = (int)(4 * sweep - drow * W);
+        for (; i < n4; i += sweep) {
+            float v[4][N];
+            long long rr = row;
+            int cc = col;
+            typename Src::Row src = S.row(rr);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                S.fetch(src, cc, f, v[k]);
+                if (++cc == W) { cc = 0; rr++; if (k < 3) src = S.row(rr); }   /* k < 3: element e + k + 1 < total, so rr < B */
+            }
+            if (S.live(0)) nt::store4(make_float4(v[0][0], v[1][0], v[2][0], v[3][0]), (float4*)(S.out(0) + head) + i);
+            if (N == 2 && S.live(1)) nt::store4(make_float4(v[0][N - 1], v[1][N - 1], v[2][N - 1], v[3][N - 1]), (float4*)(S.out(1) + head) + i);
+            row += drow; col += dcol;
+            if (col >= W) { col -= W; row++; }
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long long body_end = head + 4 * n4;
+        const int extra = (int)(head + (F.total - body_end));   /* < 8 */
+        if (t < extra) {
+            const long long e = t < head ? (long long)t : body_end + (t - head);
+            const long long row = e / W;
+            float v[N] = {};
+            S.fetch(S.row(row), (int)(e - row * W), f, v);
+            if (S.live(0)) nt::store(norm_bits(v[0]), (unsigned int*)(S.out(0) + e));
+            if (N == 2 && S.live(1)) nt::store(norm_bits(v[N - 1]), (unsigned int*)(S.out(1) + e));
+        }
+    }
+}
+/* row r of state | goal at the given strides; every input is touched once: non-temporal loads.  A row is its index: the address
+ * is formed per element, so the row hand-over of the sweep is a select, not a branch (W = 10: four float4 in ten hand over) */
+struct StridedRows {
+    static constexpr int N = 1;
+    typedef long long Row;
+    const float* __restrict__ s; long long ss; const float* __restrict__ g; long long gs; int Ds; float* __restrict__ o;
+    __device__ __forceinline__ Row row(long long r) const { return r; }
+    __device__ __forceinline__ void fetch(Row r, int col, const PolicyCols& f, float* v) const
+    {
+        v[0] = f(nt::load(col < Ds ? s + r * ss + col : g + r * gs + (col - Ds)), col);
+    }
+    __device__ __forceinline__ bool live(int) const { return true; }
+    __device__ __forceinline__ float* out(int) const { return o; }
+};
+__global__ void __launch_bounds__(256) pmg_k_policy_input(StridedRows S, int Dg, const float* __restrict__ ders, const float* __restrict__ derg,
+                                                         float cin, float cout, FlatSpan F)
+{
+    flat_sweep(S, ders, S.Ds, derg, Dg, false, cin, cout, F);
+}
+hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride, int Ds, const float* d_goal, long long goal_stride,
+                                   int Dg, long long B, const float* der_state, const float* der_goal, float clip_input,
+                                   float clip_output, float* d_out, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    const FlatSpan F = flat_span(d_out, B, Ds + Dg);
+    const StridedRows S = {d_state, state_stride, d_goal, goal_stride, Ds, d_out};
+    hipLaunchKernelGGL(pmg_k_policy_input, dim3(F.grid), dim3(256), 0, s, S, Dg, der_state, der_goal, clip_input, clip_output, F);
+    return hipGetLastError();
+}
+
+/* HER minibatches from episode rows the caller keeps in device memory (pmg_her_sample_device, DESIGN.md 3.8).
+ * The draws (include/pmg.h): SplitMix64's finaliser over a counter, four 32-bit values per sample; multiply-shift
+ * maps them onto [0, E), [0, T) and (t, T], so no address depends on device data. */
+constexpr unsigned long long HER_GOLD = 0x9E3779B97F4A7C15ull;
+__host__ __device__ __forceinline__ unsigned long long her_mix(unsigned long long z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+/* One thread per sample: the four draws -> e, t, f (idx; -1 = not relabelled), reward and flag of (achieved_goal(e, t + 1), g')
+ * from the 2 G goal floats, and the action row.  A lane per sample touches 64 different rows per wave-instruction -- the
+ * slow shape -- but only for these 2 G + A floats of a sample; the row sweep below carries the bulk.  Distance and reward
+ * are pmg_k_reward's: sq_dist and reward_of. */
+__global__ void __launch_bounds__(256) pmg_k_her_draw(PmgHer H, unsigned long long key)
+{
+    for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < H.B; b += (long long)gridDim.x * 256) {
+        const unsigned long long z = key + (4ull * (unsigned long long)b + 1ull) * HER_GOLD;
+        const unsigned long long r0 = her_mix(z) >> 32, r1 = her_mix(z + HER_GOLD) >> 32, r2 = her_mix(z + 2ull * HER_GOLD) >> 32,
+                                 r3 = her_mix(z + 3ull * HER_GOLD) >> 32;
+        const int e = (int)((r0 * (unsigned long long)H.E) >> 32);
+        const int t = (int)((r1 * (unsigned long long)H.T) >> 32);
+        const int f = r2 < H.relabel_below ? t + 1 + (int)((r3 * (unsigned long long)(H.T - t)) >> 32) : -1;
+        if (H.idx) { int* ix = H.idx + 3 * b; ix[0] = e; ix[1] = t; ix[2] = f; }   /* re-read by the sweep: plain stores */
+        if (H.reward || H.ok) {
+            const float* row = H.rows + (long long)e * H.res + (long long)t * H.rts;
+            const float* g = f >= 0 ? H.rows + (long long)e * H.res + (long long)f * H.rts + H.ago : row + H.dgo;
+            unsigned char good;
+            const float r = reward_of(sqrtf(sq_dist(row + H.rts + H.ago, g, 0, H.G)), H.thr, H.binary, good);
+            if (H.reward) nt::store(norm_bits(r), (unsigned int*)(H.reward + b));
+            if (H.ok) H.ok[b] = good;
+        }
+        if (H.action) {
+            const float* a = H.act + (long long)e * H.aes + (long long)t * H.ats;
+            for (int k = 0; k < H.A; k++) nt::store(norm_bits(a[k]), (unsigned int*)(H.action + b * H.A + k));
+        }
+    }
+}
+/* sample b of a HER batch: (e, t, f) from idx -> state(e, t), state(e, t + 1), g'.  Two streams, x[B, Ds + G] = state(e, t) | g'
+ * and xn = state(e, t + 1) | g': mode 2 fills both in one sweep and fetches g' once per sample, mode 0 / 1 fill x / xn alone.
+ * Plain loads: a replay table is read again. */
+struct HerRows {
+    static constexpr int N = 2;
+    struct Row { const float* s; const float* sn; const float* g; };
+    PmgHer H; int mode;
+    __device__ __forceinline__ Row row(long long b) const
+    {
+        const int* ix = H.idx + 3 * b;
+        const int e = ix[0], t = ix[1], f = ix[2];
+        const float* r = H.rows + (long long)e * H.res + (long long)t * H.rts;
+        const float* s = r + H.so;
+        const long long go = f >= 0 ? (long long)(f - t) * H.rts + H.ago : (long long)H.dgo;   /* g' from row (e, t) */
+        return {s, s + H.rts, r + go};
+    }
+    __device__ __forceinline__ void fetch(const Row& r, int col, const PolicyCols& f, float* v) const
+    {
+        if (col >= H.Ds) { v[0] = v[1] = f(r.g[col - H.Ds], col); return; }
+        if (mode != 1) v[0] = f(r.s[col], col);
+        if (mode != 0) v[1] = f(r.sn[col], col);
+    }
+    __device__ __forceinline__ bool live(int n) const { return mode != 1 - n; }
+    __device__ __forceinline__ float* out(int n) const { return n ? H.xn : H.x; }
+};
+__global__ void __launch_bounds__(256) pmg_k_her_rows(HerRows S, FlatSpan F)
+{
+    flat_sweep(S, S.H.der_state, S.H.Ds, S.H.der_goal, S.H.G, S.H.raw != 0, S.H.cin, S.H.cout, F);
+}
+static void launch_her_rows(const PmgHer& H, int mode, hipStream_t s)
+{
+    const FlatSpan F = flat_span(mode == 1 ? H.xn : H.x, H.B, H.Ds + H.G);
+    const HerRows S = {H, mode};
+    hipLaunchKernelGGL(pmg_k_her_rows, dim3(F.grid), dim3(256), 0, s, S, F);
+}
+hipError_t pmg_launch_her(const PmgHer& H, hipStream_t s)
+{
+    if (H.B <= 0) return hipSuccess;
+    const unsigned long long key = her_mix(H.seed ^ her_mix(H.counter + HER_GOLD));
+    const long long want = (H.B + 255) / 256;
+    hipLaunchKernelGGL(pmg_k_her_draw, dim3((unsigned)(want < (1 << 20) ? want : (1 << 20))), dim3(256), 0, s, H, key);
+    /* x and x_next share a launch iff they share their distance to a 16-byte boundary */
+    if (H.x && H.xn && (((size_t)H.x ^ (size_t)H.xn) & 15) == 0) launch_her_rows(H, 2, s);
+    else {
+        if (H.x) launch_her_rows(H, 0, s);
+        if (H.xn) launch_her_rows(H, 1, s);
+    }
+    return hipGetLastError();
+}

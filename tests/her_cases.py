@@ -318,6 +318,32 @@ def case_reward_and_flag(library, task):
                 assert (r[same] == 0).all()
 
 
+def case_reward_is_the_reward_kernels(library, task):
+    """The sampler's reward and flag against pmg_compute_reward_device on the pairs it formed, bit for bit, dense and binary:
+    achieved_goal(e, t + 1) and g' gathered on the host from the sampler's own index and uploaded four bytes behind a 16-byte
+    boundary, so that pmg_k_reward -- the kernel whose sum pmg_k_her_draw shares -- serves every item (the aligned kernels
+    sum in another shape).  B = 257: one workgroup and one item more."""
+    E, T, B = 7, 5, 257
+    for binary in (False, True):
+        with handle(library, task, num_envs=8, binary_reward=binary, distance_threshold=0.05) as env:
+            h, d = env.handle, env.handle.dims
+            rows, acts = walk_tables(d, E, T, 3 * float(np.float32(0.05)), 37)
+            with Dev(h) as dev:
+                got = sample(h, Table(h, dev, rows, acts), B, seed=10, counter=4)
+                _, _, _, ag1, g = gather(d, POL, rows, acts, got['index'])
+                d_ag, d_g = dev.alloc(ag1.nbytes + 32), dev.alloc(g.nbytes + 32)
+                d_ag, d_g = d_ag + (-d_ag) % 16 + 4, d_g + (-d_g) % 16 + 4
+                h.upload(d_ag, ag1)
+                h.upload(d_g, g)
+                d_r, d_ok = dev.alloc(4 * B), dev.alloc(B)
+                rc = h.L.lib.pmg_compute_reward_device(h.h, C.c_void_p(d_ag), C.c_void_p(d_g), C.c_int64(B), C.c_void_p(d_r), C.c_void_p(d_ok))
+                assert rc == 0, h.L.error(h.h)
+                r, ok = dev.get(d_r, B, np.float32), dev.get(d_ok, B, np.uint8)
+            assert set(np.unique(ok)) == {0, 1}, 'the fixture holds achieved and missed pairs'
+            assert np.array_equal(bits(got['reward']), bits(r)), (task, binary, np.argwhere(bits(got['reward']) != bits(r))[:4])
+            assert np.array_equal(got['goal_achieved'], ok), (task, binary, np.argwhere(got['goal_achieved'] != ok)[:4])
+
+
 # 5. edges of the sweep
 def case_sweep_edges(library):
     """block_stack observation rows, the widest W = 88 + 15: outputs off their 16-byte boundary by 4, 8 and 12 bytes, inputs by 4,

@@ -28,6 +28,11 @@ def test_reward_and_flag(hip_library, task):
     HC.case_reward_and_flag(hip_library, task)
 
 
+@pytest.mark.parametrize('task', ['push', 'block_stack'])
+def test_reward_is_the_reward_kernels(hip_library, task):
+    HC.case_reward_is_the_reward_kernels(hip_library, task)
+
+
 def test_sweep_edges(hip_library):
     HC.case_sweep_edges(hip_library)
 

@@ -26,6 +26,11 @@ def test_reward_and_flag(emu_library, task):
     HC.case_reward_and_flag(emu_library, task)
 
 
+@pytest.mark.parametrize('task', ['push', 'block_stack'])
+def test_reward_is_the_reward_kernels(emu_library, task):
+    HC.case_reward_is_the_reward_kernels(emu_library, task)
+
+
 def test_sweep_edges(emu_library):
     HC.case_sweep_edges(emu_library)
 

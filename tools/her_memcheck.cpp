@@ -1,8 +1,10 @@
-/* her_memcheck.cpp -- memory safety of pmg_her_sample_device off the GPU: a stand-alone program over the g++ emulator build
- * of the product sources (tests/emu), meant to be compiled with -fsanitize=address,undefined.  "Device" memory is malloc'd
+/* her_memcheck.cpp -- memory safety of pmg_her_sample_device and pmg_policy_input_device (the two entries of the flat sweep of
+ * csrc/pmg_learner_body.inc) off the GPU: a stand-alone program over the g++ emulator build of the product sources
+ * (tests/emu), meant to be compiled with -fsanitize=address,undefined.  "Device" memory is malloc'd
  * there, so every buffer below is sized EXACTLY and a read or write one float outside any of them stops the run.
  * Covered: time- and episode-major tables, padded strides, inputs and outputs off their 16-byte boundary, x and x_next on
- * different boundaries, NULL outputs, E = T = 1, batches on both sides of a workgroup and of the striding grid.
+ * different boundaries, NULL outputs, E = T = 1, batches on both sides of a workgroup and of the striding grid; policy-input
+ * rows of push (7 | 3) and block_stack-5 (88 | 15) at B = 1, 255, 256, 257, every out-shift 0..3 and input shifts 0..3.
  *
  * From the repository root (leak detection off: the emulator keeps its fiber stacks for the life of the process):
  *
@@ -78,9 +80,30 @@ static void run(int task, int num_block, int E, int T, bool time_major, bool pad
     pmg_destroy(env);
 }
 
+/* pmg_policy_input_device on contiguous state [B, Ds] and goal [B, Dg] rows, inputs `in_shift` and the output `out_shift` floats
+ * behind a 16-byte boundary */
+static void run_policy_input(int task, int num_block, int kind, long long B, int in_shift, int out_shift)
+{
+    pmg_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.struct_size = sizeof(cfg); cfg.task = task; cfg.num_envs = 2; cfg.num_block = num_block; cfg.binary_reward = 1;
+    cfg.max_episode_steps = 50; cfg.distance_threshold = 0.05f; cfg.seed_stride = 1;
+    env = nullptr;
+    CHECK(pmg_create(&cfg, &env));
+    pmg_dims d;
+    CHECK(pmg_get_dims(env, &d));
+    const int Ds = kind == PMG_NORM_OBSERVATION ? d.observation_dim : d.policy_state_dim, Dg = d.goal_dim;
+    Buf state((size_t)B * Ds, in_shift), goal((size_t)B * Dg, in_shift), out((size_t)B * (Ds + Dg), out_shift);
+    for (size_t i = 0; i < (size_t)B * Ds; i++) state.p[i] = (float)(i % 1000) * 0.001f;
+    for (size_t i = 0; i < (size_t)B * Dg; i++) goal.p[i] = (float)(i % 7);
+    CHECK(pmg_policy_input_device(env, kind, state.p, Ds, goal.p, Dg, B, out.p));
+    CHECK(pmg_sync(env));
+    pmg_destroy(env);
+}
+
 int main()
 {
-    int n = 0;
+    int n = 0, np = 0;
     const int tasks[3][2] = {{PMG_TASK_REACH, 0}, {PMG_TASK_PUSH, 0}, {PMG_TASK_BLOCK_STACK, 5}};
     for (const auto& tk : tasks)
         for (int layout = 0; layout < 4; layout++)
@@ -95,6 +118,11 @@ int main()
     /* from 4 * 2048 * 256 / W rows the grid strides: W = 103 */
     run(PMG_TASK_BLOCK_STACK, 5, 7, 5, true, true, 1, 1, 1, 4 * 2048 * 256 / 103 + 1, PMG_NORM_OBSERVATION, 0, 0); n++;
     run(PMG_TASK_BLOCK_STACK, 5, 7, 5, false, false, 1, 3, 2, 4 * 2048 * 256 / 103 + 1, PMG_NORM_OBSERVATION, 1, 0); n++;
-    printf("her_memcheck: %d calls of pmg_her_sample_device, no finding\n", n);
+    const int ptasks[2][3] = {{PMG_TASK_PUSH, 0, PMG_NORM_POLICY_STATE}, {PMG_TASK_BLOCK_STACK, 5, PMG_NORM_OBSERVATION}};   /* 7 | 3 and 88 | 15 */
+    for (const auto& tk : ptasks)
+        for (long long B : {1, 255, 256, 257})
+            for (int out_shift = 0; out_shift < 4; out_shift++)
+                for (int in_shift = 0; in_shift < 4; in_shift++) { run_policy_input(tk[0], tk[1], tk[2], B, in_shift, out_shift); np++; }
+    printf("her_memcheck: %d calls of pmg_her_sample_device, %d calls of pmg_policy_input_device, no finding\n", n, np);
     return 0;
 }
