@@ -249,6 +249,54 @@ typedef struct pmg_her_batch {
  * for the stream once). */
 int pmg_her_sample_device(pmg_env* env, const pmg_her_source* src, const pmg_her_batch* out);
 
+/* The actor on the device: a multi-layer perceptron on rows of floats, and the exploration policy of DDPG / HER on its output (no
+ * reference equivalent: the reference leaves the policy to its caller).  With it a rollout is two stream-ordered calls per step,
+ * pmg_act_env_device and pmg_step_device, and nothing leaves the GPU.  The caller owns the weights (device memory, read in place,
+ * never written); the library keeps no learner state.  Both calls are stream-ordered on the handle's stream, sync nothing, write
+ * only their outputs and touch no state of the handle: state rows, packed rows, RNG streams and normaliser totals stay as they are.
+ *
+ * Layers (normative).  Layer l, row r, unit j is ONE float32 chain: acc = bias[j] (+0.0 without a bias), then
+ * acc = fmaf(h[r][k], W[j][k], acc) for k = 0, 1, ..., K - 1 in ascending order; a hidden layer's output is fmaxf(acc, 0), the last
+ * layer's acc is the pre-activation z.  No split-K, no other order: a row's result does not depend on the batch it is in.
+ * (Products of an exact zero with an exact zero may follow the chain: they can turn -0 into +0 and change nothing else.)
+ *
+ * Action of global env g = env_index_offset + i, column j, A = action_dim; the draws are those of pmg_her_sample_device above
+ * with b = g A + j in place of the sample index: key = mix(seed ^ mix(counter + GOLD)), r_k = mix(key + (4 b + k + 1) GOLD) >> 32,
+ *   u1 = ((r_0 >> 8) + 1) 2^-24 in (0, 1];  u2 = (r_1 >> 8) 2^-24 in [0, 1);  v = (r_2 >> 8) 2^-23 - 1 in [-1, 1)   (exact in float32)
+ *   env g is random iff r_3 of ITS COLUMN 0 (b = g A) < ceil(random_eps 2^32)                                       (integer compare)
+ * and in float32: a0 = out_activation ? tanh(z) : z;  a1 = noise_eps > 0 ? a0 + noise_eps sqrt(-2 ln u1) cos(2 pi u2) : a0;
+ * a2 = min(max(a1, -1), 1);  a = random ? v : a2.  explore == NULL: a = a2 of a1 = a0.  So the action of env g is a function of its
+ * own row, the weights and (seed, counter, g): it depends neither on N nor on the shard. */
+typedef struct pmg_mlp {                 /* caller-owned device memory, read in place, never written */
+    int32_t struct_size;
+    int32_t num_layers;                  /* L in 1..4 */
+    int32_t width[5];                    /* width[0] = inputs, width[l + 1] = outputs of layer l; each in 1..256 */
+    int32_t out_activation;              /* 0 identity, 1 tanh; hidden layers are ReLU */
+    const float* d_weight[4];            /* layer l: [width[l + 1], width[l]] row-major, contiguous (torch nn.Linear.weight) */
+    const float* d_bias[4];              /* [width[l + 1]] or NULL (= +0.0) */
+} pmg_mlp;
+typedef struct pmg_explore {
+    int32_t struct_size, reserved;
+    float noise_eps;                     /* >= 0, finite; 0 = no noise term at all */
+    float random_eps;                    /* in [0, 1] */
+    uint64_t seed, counter;
+} pmg_explore;
+/* d_out [batch, width[L]] = out_activation(z) of the rows d_in [batch, width[0]]; in_stride / out_stride floats from row to row
+ * (>= the widths); any 4-byte alignment.  batch == 0 is a successful no-op. */
+int pmg_mlp_forward_device(pmg_env* env, const pmg_mlp* mlp, const float* d_in, int64_t in_stride, int64_t batch,
+                           float* d_out, int64_t out_stride);
+/* The actions of all N envs from the rows of the LAST step / reset: the state_kind columns and desired_goal of PMG_BUF_PACKED (under
+ * pmg_comm_overlap the buffer that name refers to at this point), read in place, every element through the normalisers' derived
+ * values as they are on the stream -- layer 0 sees exactly the row pmg_policy_input_env_device would write.  Needs width[0] ==
+ * Ds + Dg and width[L] == action_dim.  d_actions [N, action_dim] (what pmg_step_device takes); d_preact [N, action_dim] receives z, or
+ * NULL.  PMG_E_STATE before the first reset.
+ * Both calls return PMG_E_INVALID, with nothing launched, for: a wrong struct_size, L or a width out of range, an out_activation
+ * that is neither 0 nor 1, a NULL weight or output pointer (d_in too), a pointer not aligned to 4 bytes, a stride below the width,
+ * batch < 0, a state_kind that is no state kind, widths that do not match the dims, noise_eps negative or not finite, random_eps
+ * outside [0, 1] or NaN. */
+int pmg_act_env_device(pmg_env* env, const pmg_mlp* mlp, int state_kind, const pmg_explore* explore /* NULL = none */,
+                       float* d_actions /* [N, action_dim] */, float* d_preact /* [N, action_dim] or NULL */);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

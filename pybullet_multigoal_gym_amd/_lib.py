@@ -50,6 +50,16 @@ class PmgHerBatch(C.Structure):
                 ('d_goal_achieved', C.c_void_p), ('d_index', C.c_void_p)]
 
 
+class PmgMlp(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('num_layers', C.c_int32), ('width', C.c_int32 * 5), ('out_activation', C.c_int32),
+                ('d_weight', C.c_void_p * 4), ('d_bias', C.c_void_p * 4)]
+
+
+class PmgExplore(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('noise_eps', C.c_float), ('random_eps', C.c_float),
+                ('seed', C.c_uint64), ('counter', C.c_uint64)]
+
+
 class PmgError(RuntimeError):
     pass
 
@@ -69,7 +79,7 @@ class PmgLibrary:
                'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing',
                'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
-               'pmg_her_sample_device', 'pmg_device_copy']
+               'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -290,6 +300,36 @@ class PmgHandle:
         """pmg_her_sample_device with the arguments of her_structs(); stream-ordered, no host sync."""
         src, out = self.her_structs(*args, **kw)
         self._check(self.L.lib.pmg_her_sample_device(self.h, C.byref(src), C.byref(out)))
+
+    # -- actor forward + exploration (include/pmg.h, DESIGN.md 3.9) --
+    @staticmethod
+    def mlp_struct(widths, d_weights, d_biases=None, out_activation=1):
+        """pmg_mlp of a network widths[0] -> ... -> widths[L] from device pointers (integers; a bias may be None)."""
+        L = len(widths) - 1
+        if not 1 <= L <= 4 or len(d_weights) != L or (d_biases is not None and len(d_biases) != L):
+            raise ValueError('a network has 1..4 layers, one weight (and one bias or None) per layer')
+        m = PmgMlp()
+        m.struct_size, m.num_layers, m.out_activation = C.sizeof(PmgMlp), L, int(out_activation)
+        for l, w in enumerate(widths):
+            m.width[l] = int(w)
+        for l in range(L):
+            m.d_weight[l] = d_weights[l]
+            m.d_bias[l] = None if d_biases is None else d_biases[l]
+        return m
+
+    @staticmethod
+    def explore_struct(noise_eps=0.0, random_eps=0.0, seed=0, counter=0):
+        return PmgExplore(C.sizeof(PmgExplore), 0, noise_eps, random_eps, seed & (2 ** 64 - 1), counter & (2 ** 64 - 1))
+
+    def mlp_forward_device(self, mlp, d_in_ptr, in_stride, batch, d_out_ptr, out_stride):
+        """d_out [batch, width[L]] = the network on the rows d_in [batch, width[0]]; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_forward_device(self.h, C.byref(mlp), C.c_void_p(d_in_ptr), C.c_int64(in_stride), C.c_int64(batch),
+                                                      C.c_void_p(d_out_ptr), C.c_int64(out_stride)))
+
+    def act_env_device(self, mlp, state_kind, d_actions_ptr, d_preact_ptr=None, explore=None):
+        """Actions [N, action_dim] of the rows of the last step / reset (what step_device takes); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_act_env_device(self.h, C.byref(mlp), C.c_int(state_kind), C.byref(explore) if explore is not None else None,
+                                                  C.c_void_p(d_actions_ptr), C.c_void_p(d_preact_ptr) if d_preact_ptr else None))
 
     def timing_reset(self):
         self._check(self.L.lib.pmg_timing_reset(self.h))

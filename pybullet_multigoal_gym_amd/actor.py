@@ -1,0 +1,125 @@
+"""The actor of a goal-conditioned learner on the device: a small MLP and DDPG / HER's exploration on its output.
+
+Host-side face of ``pmg_mlp_forward_device`` and ``pmg_act_env_device`` (include/pmg.h).  All arithmetic happens
+in the HIP library; this file uploads the network, validates shapes and moves buffers.  The library keeps no learner state: the
+weights live in buffers this object owns until ``close()`` (or the next ``load``).  A device-resident rollout is two
+stream-ordered calls per step and nothing leaves the GPU:
+
+    env.actor.load(weights, biases)                         # torch layout: weights[l] is [out, in]
+    d_actions = h.device_alloc(4 * N * A)                   # once
+    env.actor.act_device(d_actions, noise_eps=0.2, random_eps=0.3, seed=s, counter=t)
+    h.step_device(d_actions)
+"""
+import numpy as np
+
+from ._lib import PMG_NORM_OBSERVATION, PMG_NORM_POLICY_STATE
+
+KINDS = {'observation': PMG_NORM_OBSERVATION, 'policy_state': PMG_NORM_POLICY_STATE}
+ACTIVATIONS = {'identity': 0, 'tanh': 1}
+MAX_LAYERS, MAX_WIDTH = 4, 256
+
+
+class Actor:
+    """``env.actor``: an MLP with ReLU hidden layers on the env's device, and the actions of the env's current rows."""
+
+    def __init__(self, env):
+        self._env = env
+        self._h = env.handle
+        self._ptrs = []
+        self._mlp = None
+        self.widths = None
+
+    def load(self, weights, biases=None, out_activation='tanh'):
+        """Upload a network: weights[l] is [out_l, in_l] (torch ``nn.Linear.weight``), biases[l] is [out_l] or None; 1..4 layers
+        of 1..256 units, each layer's inputs the outputs of the one before.  Replaces a network loaded earlier."""
+        if out_activation not in ACTIVATIONS:
+            raise ValueError('out_activation must be one of %s, not %r' % (sorted(ACTIVATIONS), out_activation))
+        weights = [np.ascontiguousarray(w, np.float32) for w in weights]
+        L = len(weights)
+        if not 1 <= L <= MAX_LAYERS:
+            raise ValueError('a network has 1..%d layers, not %d' % (MAX_LAYERS, L))
+        biases = [None] * L if biases is None else [None if b is None else np.ascontiguousarray(b, np.float32) for b in biases]
+        if len(biases) != L:
+            raise ValueError('%d biases for %d layers' % (len(biases), L))
+        for l, (w, b) in enumerate(zip(weights, biases)):
+            if w.ndim != 2 or not (1 <= w.shape[0] <= MAX_WIDTH and 1 <= w.shape[1] <= MAX_WIDTH):
+                raise ValueError('weights[%d] must be [out, in] with both in 1..%d, not %s' % (l, MAX_WIDTH, w.shape))
+            if l and w.shape[1] != weights[l - 1].shape[0]:
+                raise ValueError('weights[%d] takes %d inputs, layer %d has %d outputs' % (l, w.shape[1], l - 1, weights[l - 1].shape[0]))
+            if b is not None and b.shape != (w.shape[0],):
+                raise ValueError('biases[%d] must have shape (%d,), not %s' % (l, w.shape[0], b.shape))
+        self.close()
+        h = self._h
+        d_w, d_b = [], []
+        for w, b in zip(weights, biases):
+            for a, out in ((w, d_w), (b, d_b)):
+                if a is None:
+                    out.append(None)
+                    continue
+                p = h.device_alloc(a.nbytes)
+                self._ptrs.append(p)
+                h.upload(p, a)
+                out.append(p)
+        self.widths = [weights[0].shape[1]] + [w.shape[0] for w in weights]
+        self._mlp = h.mlp_struct(self.widths, d_w, d_b, ACTIVATIONS[out_activation])
+
+    def _loaded(self):
+        if self._mlp is None:
+            raise ValueError('no network: call load() first')
+        return self._mlp
+
+    def forward(self, x):
+        """x [..., width[0]] -> out_activation(z) [..., width[L]]."""
+        mlp, h = self._loaded(), self._h
+        x = np.ascontiguousarray(x, np.float32)
+        K, A = self.widths[0], self.widths[-1]
+        if x.ndim == 0 or x.shape[-1] != K:
+            raise ValueError('x %s must have a shape ending in %d' % (x.shape, K))
+        B = x.size // K
+        out = np.empty(x.shape[:-1] + (A,), np.float32)
+        if B == 0:
+            return out
+        d_in, d_out = h.device_alloc(x.nbytes), None
+        try:
+            d_out = h.device_alloc(out.nbytes)
+            h.upload(d_in, x)
+            h.mlp_forward_device(mlp, d_in, K, B, d_out, A)
+            h.sync()
+            h.download(out, d_out)
+        finally:
+            h.device_free(d_in)
+            if d_out is not None:
+                h.device_free(d_out)
+        return out
+
+    def act_device(self, d_actions_ptr, kind='policy_state', noise_eps=0.0, random_eps=0.0, seed=0, counter=0, d_preact_ptr=None):
+        """Actions [N, A] of the env's current rows into device memory (then ``handle.step_device(d_actions_ptr)``); on the
+        handle's stream, no host sync.  The draws are a pure function of (seed, counter, global env index, column)."""
+        if kind not in KINDS:
+            raise ValueError('kind must be one of %s, not %r' % (sorted(KINDS), kind))
+        if not float(noise_eps) >= 0.0 or not np.isfinite(noise_eps):
+            raise ValueError('noise_eps %r must be finite and >= 0' % (noise_eps,))
+        if not 0.0 <= float(random_eps) <= 1.0:
+            raise ValueError('random_eps %r is outside [0, 1]' % (random_eps,))
+        ex = self._h.explore_struct(float(noise_eps), float(random_eps), int(seed), int(counter))
+        self._h.act_env_device(self._loaded(), KINDS[kind], d_actions_ptr, d_preact_ptr, ex)
+
+    def act(self, kind='policy_state', noise_eps=0.0, random_eps=0.0, seed=0, counter=0):
+        """-> actions [N, A] of the env's current rows (numpy)."""
+        h = self._h
+        out = np.empty((h.N, h.dims.action_dim), np.float32)
+        d_out = h.device_alloc(out.nbytes)
+        try:
+            self.act_device(d_out, kind, noise_eps, random_eps, seed, counter)
+            h.sync()
+            h.download(out, d_out)
+        finally:
+            h.device_free(d_out)
+        return out
+
+    def close(self):
+        """Free the uploaded network."""
+        if getattr(self._h, 'h', None):
+            for p in self._ptrs:
+                self._h.device_free(p)
+        self._ptrs, self._mlp, self.widths = [], None, None

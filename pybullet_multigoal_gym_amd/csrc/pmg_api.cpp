@@ -945,6 +945,79 @@ int pmg_her_sample_device(pmg_env* e, const pmg_her_source* src, const pmg_her_b
     return PMG_OK;
 }
 
+/* ---- actor forward + exploration ---- */
+/* the network of a call, validated -> M (L, widths, activation, weights); 0 or PMG_E_INVALID */
+static int mlp_of(pmg_env* e, const pmg_mlp* mlp, const char* who, PmgMlp& M)
+{
+    if (!mlp) return fail(e, PMG_E_INVALID, "%s: mlp is null", who);
+    if (mlp->struct_size != (int32_t)sizeof(pmg_mlp)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, mlp->struct_size, sizeof(pmg_mlp));
+    if (mlp->num_layers < 1 || mlp->num_layers > 4) return fail(e, PMG_E_INVALID, "%s: num_layers %d is outside 1..4", who, mlp->num_layers);
+    if (mlp->out_activation != 0 && mlp->out_activation != 1) return fail(e, PMG_E_INVALID, "%s: out_activation %d is neither 0 (identity) nor 1 (tanh)", who, mlp->out_activation);
+    memset(&M, 0, sizeof(M));
+    M.L = mlp->num_layers; M.out_act = mlp->out_activation;
+    for (int l = 0; l <= M.L; l++) {
+        if (mlp->width[l] < 1 || mlp->width[l] > 256) return fail(e, PMG_E_INVALID, "%s: width[%d] = %d is outside 1..256", who, l, mlp->width[l]);
+        M.width[l] = mlp->width[l];
+    }
+    for (int l = 0; l < M.L; l++) {
+        if (!mlp->d_weight[l]) return fail(e, PMG_E_INVALID, "%s: d_weight[%d] is null", who, l);
+        if ((((size_t)mlp->d_weight[l] | (size_t)mlp->d_bias[l]) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: the weights of layer %d are not aligned to 4 bytes", who, l);
+        M.w[l] = mlp->d_weight[l]; M.b[l] = mlp->d_bias[l];
+    }
+    return PMG_OK;
+}
+
+int pmg_mlp_forward_device(pmg_env* e, const pmg_mlp* mlp, const float* d_in, int64_t in_stride, int64_t batch, float* d_out, int64_t out_stride)
+{
+    if (!e) return PMG_E_INVALID;
+    PmgMlp M;
+    if (int rc = mlp_of(e, mlp, "pmg_mlp_forward_device", M)) return rc;
+    if (!d_in || !d_out) return fail(e, PMG_E_INVALID, "pmg_mlp_forward_device: null pointer");
+    if ((((size_t)d_in | (size_t)d_out) & 3) != 0) return fail(e, PMG_E_INVALID, "pmg_mlp_forward_device: a row pointer is not aligned to 4 bytes");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_mlp_forward_device: batch %lld is negative", (long long)batch);
+    if (in_stride < M.width[0] || out_stride < M.width[M.L])
+        return fail(e, PMG_E_INVALID, "pmg_mlp_forward_device: strides %lld / %lld are smaller than the widths %d / %d", (long long)in_stride, (long long)out_stride, M.width[0], M.width[M.L]);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = batch; M.out = d_out; M.out_stride = out_stride;
+    HIP_TRY(e, pmg_launch_mlp_forward(M, d_in, in_stride, e->stream));
+    return PMG_OK;
+}
+
+int pmg_act_env_device(pmg_env* e, const pmg_mlp* mlp, int state_kind, const pmg_explore* explore, float* d_actions, float* d_preact)
+{
+    if (!e) return PMG_E_INVALID;
+    PmgMlp M;
+    if (int rc = mlp_of(e, mlp, "pmg_act_env_device", M)) return rc;
+    const pmg_env::Norm* found = state_norm_of(e, state_kind, "pmg_act_env_device"); if (!found) return PMG_E_INVALID;
+    const pmg_env::Norm& ns = *found;
+    const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
+    const pmg_dims& d = e->dims;
+    if (M.width[0] != ns.D + ng.D || M.width[M.L] != d.action_dim)
+        return fail(e, PMG_E_INVALID, "pmg_act_env_device: the network maps %d -> %d, the env needs %d + %d -> %d", M.width[0], M.width[M.L], ns.D, ng.D, d.action_dim);
+    if (!d_actions) return fail(e, PMG_E_INVALID, "pmg_act_env_device: d_actions is null");
+    if ((((size_t)d_actions | (size_t)d_preact) & 3) != 0) return fail(e, PMG_E_INVALID, "pmg_act_env_device: an output is not aligned to 4 bytes");
+    if (explore) {
+        if (explore->struct_size != (int32_t)sizeof(pmg_explore)) return fail(e, PMG_E_INVALID, "pmg_act_env_device: explore struct_size %d != %zu", explore->struct_size, sizeof(pmg_explore));
+        if (!(explore->noise_eps >= 0.f) || std::isinf(explore->noise_eps)) return fail(e, PMG_E_INVALID, "pmg_act_env_device: noise_eps %g must be finite and >= 0", (double)explore->noise_eps);
+        if (!(explore->random_eps >= 0.f && explore->random_eps <= 1.f)) return fail(e, PMG_E_INVALID, "pmg_act_env_device: random_eps %g is outside [0, 1]", (double)explore->random_eps);
+        M.explore = 1; M.noise_eps = explore->noise_eps;
+        M.seed = explore->seed; M.counter = explore->counter;
+        M.random_below = (unsigned long long)ceil((double)explore->random_eps * 4294967296.0);   /* r_3 is an integer: r_3 < p 2^32 iff r_3 < ceil(p 2^32) */
+    }
+    if (!e->ever_reset) return fail(e, PMG_E_STATE, "pmg_act_env_device: reset() must be called (for all envs) first");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = d.num_envs; M.out = d_preact; M.out_stride = d.action_dim; M.actions = d_actions; M.env0 = e->cfg.env_index_offset;
+    PmgMlpEnv E;
+    E.rows = e->P.out;   /* the buffer of the LAST step, as pmg_device_ptr(PMG_BUF_PACKED) */
+    E.stride = d.packed_dim;
+    E.so = state_kind == PMG_NORM_OBSERVATION ? 0 : d.observation_dim;
+    E.dgo = d.observation_dim + d.policy_state_dim + d.goal_dim;
+    E.Ds = ns.D; E.Dg = ng.D; E.der_state = ns.der; E.der_goal = ng.der; E.cin = e->norm_clip_in; E.cout = e->norm_clip_out;
+    HIP_TRY(e, pmg_launch_mlp_act(M, E, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

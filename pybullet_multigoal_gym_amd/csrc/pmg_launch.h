@@ -45,4 +45,28 @@ struct PmgHer {
     float* x; float* xn; float* action; float* reward; unsigned char* ok; int* idx;
 };
 hipError_t pmg_launch_her(const PmgHer& H, hipStream_t s);
+
+/* actor forward + exploration (pmg_mlp_forward_device, pmg_act_env_device): the network and the outputs, validated by
+ * the caller.  w[l] = [width[l + 1], width[l]] row-major, b[l] = [width[l + 1]] or null.  out: forward = [B, width[L]] rows of out_activation(z)
+ * at out_stride; act = the pre-activations z (may be null), and actions [B, width[L]] contiguous = the action of global env env0 + row. */
+struct PmgMlp {
+    int L, width[5], out_act;
+    const float* w[4]; const float* b[4];
+    long long B;
+    float* out; long long out_stride;
+    float* actions; long long env0;
+    int explore; float noise_eps;                       /* explore == 0: a = clip(out_activation(z)), no draw */
+    unsigned long long seed, counter, random_below;     /* random iff r_3 < random_below = ceil(random_eps * 2^32) */
+    unsigned long long key;                             /* mix(seed ^ mix(counter + GOLD)): set by the launcher */
+};
+/* the input rows of the act entry: state columns [so, so + Ds) and desired-goal columns [dgo, dgo + Dg) of packed rows, through
+ * policy_norm with the derived arrays of the two normalisers */
+struct PmgMlpEnv {
+    const float* rows; long long stride;
+    int so, dgo, Ds, Dg;
+    const float* der_state; const float* der_goal;
+    float cin, cout;
+};
+hipError_t pmg_launch_mlp_forward(const PmgMlp& M, const float* d_in, long long in_stride, hipStream_t s);
+hipError_t pmg_launch_mlp_act(const PmgMlp& M, const PmgMlpEnv& E, hipStream_t s);
 #endif

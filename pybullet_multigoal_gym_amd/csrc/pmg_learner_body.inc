@@ -1,5 +1,5 @@
 /* pmg_learner_body.inc -- the learner-side kernels and their launchers (included by pmg_kernels.hip): rewards of [B, G] batches,
- * the running normaliser, policy-input rows and HER minibatches (DESIGN.md 3.6-3.8).  None of them touches EnvParams.  What two
+ * the running normaliser, policy-input rows, HER minibatches and the actor forward (DESIGN.md 3.6-3.9).  None of them touches EnvParams.  What two
  * kernels share has ONE definition, so that they agree bit for bit by construction: reward_of, sq_dist, policy_norm, flat_sweep. */
 /* distance, threshold, binary -> reward value and flag: the one definition (all three reward kernels and pmg_k_her_draw) */
 __device__ __forceinline__ float reward_of(float d, float thr, int binary, unsigned char& ok)
@@ -433,5 +433,199 @@ hipError_t pmg_launch_her(const PmgHer& H, hipStream_t s)
         if (H.x) launch_her_rows(H, 0, s);
         if (H.xn) launch_her_rows(H, 1, s);
     }
+    return hipGetLastError();
+}
+
+/* Actor forward on the device (pmg_mlp_forward_device, pmg_act_env_device; DESIGN.md 3.9): a multi-layer perceptron of up to four
+ * layers of up to 256 units on rows of floats, and for the act entry the exploration epilogue.  A workgroup owns MLP_ROWS = 32
+ * rows and runs ALL layers on them: the activations stay in LDS, wavefront w owns the 32-unit strips w and w + 4 of a layer and
+ * keeps their 32 x 32 results in registers (2 x 16) across the barrier behind which the tile is overwritten -- one buffer.  The last
+ * layer leaves z there too, and a thread per (row, unit) writes the outputs.
+ * Arithmetic (normative): unit j of a row is ONE float32 chain acc = bias[j]; acc = fmaf(h[k], W[j][k], acc), k ascending; the
+ * f32-input MFMA is bit for bit that chain (two k per instruction, lower k first).  K odd: the last step multiplies a zero the
+ * tile holds in column K by a zero that stands in for W[j][K]; the lanes of units beyond the layer's width run on row 0 of W and
+ * their results are dropped.
+ * B operand: read as dwords straight from the caller's [out, in] row-major weights, lane (unit, k parity) walking ITS row.  With 32
+ * rows per workgroup = M of the instruction every weight is used by exactly one lane of one wavefront once, so staging through
+ * LDS would add a write and a read per element and save none; a lane's 128-byte line serves its next 15 steps from L1. */
+constexpr int MLP_ROWS = 32;             /* rows of a workgroup's tile = M of the matrix step */
+constexpr int MLP_MAXW = 256;            /* widest layer */
+constexpr int MLP_LD = MLP_MAXW + 2;     /* floats from row to row of the tile: = 2 (mod 64), the 32 rows x 2 k of an A read hit 64 banks */
+#ifdef PMG_EMULATE
+struct MlpAcc { float v[16]; float& operator[](int i) { return v[i]; } float operator[](int i) const { return v[i]; } };
+#else
+typedef float MlpAcc __attribute__((ext_vector_type(16)));
+#endif
+/* C/D map of the 32 x 32 tile: lane l holds column l & 31, register reg of it is this row */
+__device__ __forceinline__ int mlp_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+/* v, or +0.0 where keep is false, without a select: a select fed by a load becomes a branch around the load, and the loop then
+ * waits for every load on its own */
+__device__ __forceinline__ float mlp_keep(float v, bool keep)
+{
+    unsigned int u;
+    __builtin_memcpy(&u, &v, 4);
+    u &= keep ? 0xffffffffu : 0u;
+    __builtin_memcpy(&v, &u, 4);
+    return v;
+}
+/* THE matrix step, k0 even: acc[row][unit] = fmaf(tile[row][k0 + 1], W[unit][k0 + 1], fmaf(tile[row][k0], W[unit][k0], acc[row][unit]))
+ * for the 32 rows of the tile and the 32 units of a strip; wrow = row of W of THIS lane's unit (lane & 31).  TAIL: the last step
+ * of an odd K, k0 = K - 1: column K of the tile holds zeros and +0.0 stands in for W[unit][K].  Device: v_mfma_f32_32x32x2_f32,
+ * A = tile[l & 31][k0 + (l >> 5)], B = W[unit l & 31][k0 + (l >> 5)].  Emulator: the same tile as fmaf over the lane's own 16
+ * results, A and B read where the device body reads them (no lane exchange). */
+template <bool TAIL>
+__device__ __forceinline__ void mlp_mma(const float* tile, const float* __restrict__ wrow, int k0, int lane, MlpAcc& acc)
+{
+#ifndef PMG_EMULATE
+    const int h = lane >> 5;
+    const float a = tile[(lane & 31) * MLP_LD + k0 + h];
+    const float b = TAIL ? mlp_keep(wrow[k0], h == 0) : wrow[k0 + h];
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+#else
+    for (int reg = 0; reg < 16; reg++) {
+        const float* a = tile + mlp_row(reg, lane) * MLP_LD + k0;
+        acc[reg] = fmaf(a[1], TAIL ? 0.f : wrow[k0 + 1], fmaf(a[0], wrow[k0], acc[reg]));
+    }
+#endif
+}
+/* all K steps of a layer for the NS = 1 or 2 strips of a wavefront, which share the A operand.  Eight steps are written out: their
+ * 8 NS weight loads are in flight together (the optimizer does not unroll this loop at a run-time trip count on request) */
+template <int NS>
+__device__ __forceinline__ void mlp_chain(const float* tile, const float* __restrict__ w0, const float* __restrict__ w1, int K, int lane,
+                                          MlpAcc& acc0, MlpAcc& acc1)
+{
+    const int K16 = K & ~15, Ke = K & ~1;
+    for (int k0 = 0; k0 < K16; k0 += 16) {
+#pragma unroll
+        for (int u = 0; u < 16; u += 2) {
+            mlp_mma<false>(tile, w0, k0 + u, lane, acc0);
+            if (NS == 2) mlp_mma<false>(tile, w1, k0 + u, lane, acc1);
+        }
+    }
+    for (int k0 = K16; k0 < Ke; k0 += 2) {
+        mlp_mma<false>(tile, w0, k0, lane, acc0);
+        if (NS == 2) mlp_mma<false>(tile, w1, k0, lane, acc1);
+    }
+    if (K & 1) {
+        mlp_mma<true>(tile, w0, Ke, lane, acc0);
+        if (NS == 2) mlp_mma<true>(tile, w1, Ke, lane, acc1);
+    }
+}
+/* the row sources: at(r, col) = element col of input row r */
+struct MlpRawRows {
+    const float* __restrict__ in; long long stride;
+    __device__ __forceinline__ float at(long long r, int col) const { return in[r * stride + col]; }
+};
+/* state | desired_goal columns of packed rows through policy_norm: the row pmg_k_policy_input writes, element by element */
+struct MlpEnvRows {
+    PmgMlpEnv E;
+    __device__ __forceinline__ float at(long long r, int col) const
+    {
+        const bool st = col < E.Ds;
+        const int c = st ? col : col - E.Ds, D = st ? E.Ds : E.Dg;
+        const float* __restrict__ der = st ? E.der_state : E.der_goal;
+        return policy_norm(E.rows[r * E.stride + (st ? E.so : E.dgo) + c], der[c], der[2 * D + c], E.cin, E.cout);
+    }
+};
+/* pre-activation z of column j of global env g -> action (include/pmg.h): HER's generator with b = g A + j as the sample index */
+__device__ __forceinline__ float mlp_action(const PmgMlp& M, float z, unsigned long long g, int j, int A)
+{
+    float a = M.out_act ? tanhf(z) : z;
+    if (!M.explore) return fminf(fmaxf(a, -1.f), 1.f);
+    const unsigned long long z0 = M.key + (4ull * (g * (unsigned long long)A) + 1ull) * HER_GOLD;   /* column 0 of the env */
+    const unsigned long long zb = z0 + 4ull * (unsigned long long)j * HER_GOLD;
+    if (M.noise_eps > 0.f) {
+        const unsigned int r0 = (unsigned int)(her_mix(zb) >> 32), r1 = (unsigned int)(her_mix(zb + HER_GOLD) >> 32);
+        const float u1 = (float)((r0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r1 >> 8) * 0x1p-24f;
+        a = a + M.noise_eps * sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    }
+    a = fminf(fmaxf(a, -1.f), 1.f);
+    if ((her_mix(z0 + 3ull * HER_GOLD) >> 32) < M.random_below) {
+        const unsigned int r2 = (unsigned int)(her_mix(zb + 2ull * HER_GOLD) >> 32);
+        a = (float)(r2 >> 8) * 0x1p-23f - 1.f;
+    }
+    return a;
+}
+template <class Src, bool ACT>
+__global__ void __launch_bounds__(256) pmg_k_mlp(Src S, PmgMlp M)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const long long ntiles = (M.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        {   /* the input rows, lanes along the columns; rows past the batch and column K of an odd K: zeros.  Every address is valid
+             * (clamped), so the loads of a thread are in flight together */
+            const int K = M.width[0], Kp = (K + 1) & ~1;
+#pragma unroll 4
+            for (int i = t; i < MLP_ROWS * Kp; i += 256) {
+                const int r = i / Kp, c = i - r * Kp;
+                const bool in = row0 + r < M.B && c < K;
+                tile[r * MLP_LD + c] = mlp_keep(S.at(row0 + r < M.B ? row0 + r : M.B - 1, c < K ? c : K - 1), in);
+            }
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int l = 0; l < M.L; l++) {
+            const int K = M.width[l], Nn = M.width[l + 1];
+            const float* __restrict__ W = M.w[l];
+            const float* __restrict__ bias = M.b[l];
+            const int u0 = 32 * wave + col, u1 = u0 + 128;            /* this lane's unit in the strips wave and wave + 4 */
+            const bool live0 = u0 < Nn, live1 = u1 < Nn, strip0 = 32 * wave < Nn, strip1 = 32 * wave + 128 < Nn;
+            /* a unit past the width runs on row 0 of W: valid addresses, results never used */
+            const float* w0 = W + (long long)(live0 ? u0 : 0) * K;
+            const float* w1 = W + (long long)(live1 ? u1 : 0) * K;
+            const float b0 = bias ? bias[live0 ? u0 : 0] : 0.f, b1 = bias ? bias[live1 ? u1 : 0] : 0.f;
+            MlpAcc acc0, acc1;
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) { acc0[reg] = b0; acc1[reg] = b1; }
+            if (strip1) mlp_chain<2>(tile, w0, w1, K, lane, acc0, acc1);
+            else if (strip0) mlp_chain<1>(tile, w0, w1, K, lane, acc0, acc1);
+            const bool hidden = l + 1 < M.L;
+            __syncthreads();                                         /* every wavefront has read the layer's input */
+            /* whole strips: a unit past the width becomes +0.0, the next layer's padding */
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                if (strip0) tile[mlp_row(reg, lane) * MLP_LD + u0] = live0 ? (hidden ? fmaxf(acc0[reg], 0.f) : acc0[reg]) : 0.f;
+                if (strip1) tile[mlp_row(reg, lane) * MLP_LD + u1] = live1 ? (hidden ? fmaxf(acc1[reg], 0.f) : acc1[reg]) : 0.f;
+            }
+            __syncthreads();
+        }
+        {   /* the tile holds z: thread per (row, unit), units along the lanes */
+            const int A = M.width[M.L];
+            for (int i = t; i < MLP_ROWS * A; i += 256) {
+                const int r = i / A, j = i - r * A;
+                const long long row = row0 + r;
+                if (row >= M.B) break;
+                const float z = tile[r * MLP_LD + j];
+                if (ACT) {
+                    if (M.out) M.out[row * M.out_stride + j] = z;
+                    M.actions[row * A + j] = mlp_action(M, z, (unsigned long long)(M.env0 + row), j, A);
+                } else
+                    M.out[row * M.out_stride + j] = M.out_act ? tanhf(z) : z;
+            }
+        }
+        __syncthreads();                                             /* the next tile's rows overwrite this one's */
+    }
+}
+static unsigned mlp_grid(long long B)
+{
+    const long long want = (B + MLP_ROWS - 1) / MLP_ROWS;
+    return (unsigned)(want < (1 << 20) ? want : (1 << 20));
+}
+hipError_t pmg_launch_mlp_forward(const PmgMlp& M, const float* d_in, long long in_stride, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    const MlpRawRows S = {d_in, in_stride};
+    hipLaunchKernelGGL((pmg_k_mlp<MlpRawRows, false>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_mlp_act(const PmgMlp& net, const PmgMlpEnv& E, hipStream_t s)
+{
+    if (net.B <= 0) return hipSuccess;
+    PmgMlp M = net;
+    M.key = her_mix(M.seed ^ her_mix(M.counter + HER_GOLD));
+    const MlpEnvRows S = {E};
+    hipLaunchKernelGGL((pmg_k_mlp<MlpEnvRows, true>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M);
     return hipGetLastError();
 }

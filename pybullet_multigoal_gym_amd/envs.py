@@ -285,8 +285,19 @@ class KukaVecEnv:
             self._her = HerSampler(self)
         return self._her
 
+    @property
+    def actor(self):
+        """The actor network of this env on the device (actor.Actor): forward passes and actions with exploration, created on
+        first access."""
+        if getattr(self, '_actor', None) is None:
+            from .actor import Actor
+            self._actor = Actor(self)
+        return self._actor
+
     def close(self):
         if not self._closed:
+            if getattr(self, '_actor', None) is not None:
+                self._actor.close()
             self.handle.close()
             self._closed = True
 
