@@ -297,6 +297,43 @@ int pmg_mlp_forward_device(pmg_env* env, const pmg_mlp* mlp, const float* d_in, 
 int pmg_act_env_device(pmg_env* env, const pmg_mlp* mlp, int state_kind, const pmg_explore* explore /* NULL = none */,
                        float* d_actions /* [N, action_dim] */, float* d_preact /* [N, action_dim] or NULL */);
 
+/* The critic Q(x, a) and the TD target of a DDPG / HER update on the device, forward only (no reference equivalent).  Both entries
+ * take networks as pmg_mlp above, are stream-ordered on the handle's stream, sync nothing, write only their outputs and touch no
+ * state of the handle.  The learner loop is pmg_her_sample_device -> pmg_td_target_device on its d_x_next and d_reward; gradients
+ * and optimiser steps are the caller's.
+ *
+ * pmg_q_device: q[b] (at d_q + b * q_stride) = out_activation(z) of the critic on the row x[b] | a[b]: column c < x_dim is
+ * x[b][c], column x_dim + j is a[b][j]; both tables are read in place at their own strides.  It is the layer chain above on that
+ * row: bit for bit what pmg_mlp_forward_device returns on a table that holds the concatenated rows.
+ *
+ * pmg_td_target_device (normative), float32 throughout, Dx = actor.width[0], A = actor.width[L], row x' of d_x_next:
+ *   a'[j] = min(max(actor.out_activation ? tanhf(z[j]) : z[j], -1), 1)      z = the actor's chain on x'
+ *   q'    = critic.out_activation(z_c), z_c = the critic's chain on the row x' | a' (column c < Dx is x'[c], column Dx + j is a'[j])
+ *   t     = terminal ? r : fmaf(gamma, q', r)
+ *   y     = fminf(fmaxf(t, clip_lo), clip_hi)
+ * A sample's result does not depend on the batch it is in.  (fminf / fmaxf of -0.0 and +0.0 may return either zero: where t and a clip
+ * are zeros of opposite sign, the sign of y's zero is not specified.)
+ *
+ * PMG_E_INVALID, with nothing launched: everything the calls above reject in a network, for either network; critic.width[0] !=
+ * x_dim + a_dim (pmg_q_device) or != Dx + A (so Dx + A <= 256); critic.width[L] != 1; x_dim < 1 or a_dim < 1; a wrong
+ * struct_size; a NULL required pointer; a pointer not aligned to 4 bytes (d_terminal: any address); a stride below its width;
+ * batch < 0; gamma negative or not finite; clip_lo > clip_hi or either a NaN.  batch == 0 is a successful no-op. */
+int pmg_q_device(pmg_env* env, const pmg_mlp* critic, const float* d_x, int64_t x_stride, int32_t x_dim,
+                 const float* d_a, int64_t a_stride, int32_t a_dim, int64_t batch, float* d_q, int64_t q_stride);
+typedef struct pmg_td_target {
+    int32_t struct_size, reserved;
+    float gamma;                         /* finite, >= 0 */
+    float clip_lo, clip_hi;              /* clip_lo <= clip_hi; -inf / +inf = no clip; NaN invalid */
+    int64_t batch;
+    const float* d_x_next; int64_t x_stride;   /* [B, Dx] at x_stride floats from row to row, e.g. pmg_her_batch.d_x_next */
+    const float* d_reward;               /* [B] */
+    const uint8_t* d_terminal;           /* [B] or NULL; non-zero: no bootstrap term, t = r */
+    float* d_y;                          /* [B]     required */
+    float* d_q_next;                     /* [B]     or NULL: q' */
+    float* d_next_action;                /* [B, A]  or NULL: a' */
+} pmg_td_target;
+int pmg_td_target_device(pmg_env* env, const pmg_mlp* actor_target, const pmg_mlp* critic_target, const pmg_td_target* td);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

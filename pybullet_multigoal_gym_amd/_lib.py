@@ -60,6 +60,12 @@ class PmgExplore(C.Structure):
                 ('seed', C.c_uint64), ('counter', C.c_uint64)]
 
 
+class PmgTdTarget(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gamma', C.c_float), ('clip_lo', C.c_float), ('clip_hi', C.c_float),
+                ('batch', C.c_int64), ('d_x_next', C.c_void_p), ('x_stride', C.c_int64), ('d_reward', C.c_void_p), ('d_terminal', C.c_void_p),
+                ('d_y', C.c_void_p), ('d_q_next', C.c_void_p), ('d_next_action', C.c_void_p)]
+
+
 class PmgError(RuntimeError):
     pass
 
@@ -79,7 +85,7 @@ class PmgLibrary:
                'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing',
                'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
-               'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device']
+               'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -330,6 +336,23 @@ class PmgHandle:
         """Actions [N, action_dim] of the rows of the last step / reset (what step_device takes); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_act_env_device(self.h, C.byref(mlp), C.c_int(state_kind), C.byref(explore) if explore is not None else None,
                                                   C.c_void_p(d_actions_ptr), C.c_void_p(d_preact_ptr) if d_preact_ptr else None))
+
+    # -- critic and TD target (include/pmg.h, DESIGN.md 3.10) --
+    @staticmethod
+    def td_struct(batch, d_x_next, x_stride, d_reward, d_y, gamma, clip_lo=-float('inf'), clip_hi=float('inf'), d_terminal=None, d_q_next=None,
+                  d_next_action=None):
+        """pmg_td_target from device pointers (integers or None)."""
+        return PmgTdTarget(C.sizeof(PmgTdTarget), 0, gamma, clip_lo, clip_hi, batch, d_x_next, x_stride, d_reward, d_terminal, d_y, d_q_next,
+                           d_next_action)
+
+    def q_device(self, critic, d_x_ptr, x_stride, x_dim, d_a_ptr, a_stride, a_dim, batch, d_q_ptr, q_stride=1):
+        """d_q [batch] = the critic on the rows x[b] | a[b] of two tables read in place; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_q_device(self.h, C.byref(critic), C.c_void_p(d_x_ptr), C.c_int64(x_stride), C.c_int32(x_dim), C.c_void_p(d_a_ptr),
+                                            C.c_int64(a_stride), C.c_int32(a_dim), C.c_int64(batch), C.c_void_p(d_q_ptr), C.c_int64(q_stride)))
+
+    def td_target_device(self, actor_target, critic_target, td):
+        """y = clip(r + gamma Q'(x', pi'(x'))) of a td_struct(); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_td_target_device(self.h, C.byref(actor_target), C.byref(critic_target), C.byref(td)))
 
     def timing_reset(self):
         self._check(self.L.lib.pmg_timing_reset(self.h))

@@ -19,6 +19,39 @@ ACTIVATIONS = {'identity': 0, 'tanh': 1}
 MAX_LAYERS, MAX_WIDTH = 4, 256
 
 
+def upload_network(h, weights, biases=None, outputs=None):
+    """Check a network (weights[l] is [out_l, in_l], biases[l] is [out_l] or None; 1..MAX_LAYERS layers of 1..MAX_WIDTH units, each layer's
+    inputs the outputs of the one before; ``outputs``: the width the last layer must have) and upload it -> every device pointer (to free),
+    widths, weight pointers, bias pointers.  Nothing is allocated when a check fails.  Shared by ``Actor.load`` and ``Critic.load``."""
+    weights = [np.ascontiguousarray(w, np.float32) for w in weights]
+    L = len(weights)
+    if not 1 <= L <= MAX_LAYERS:
+        raise ValueError('a network has 1..%d layers, not %d' % (MAX_LAYERS, L))
+    biases = [None] * L if biases is None else [None if b is None else np.ascontiguousarray(b, np.float32) for b in biases]
+    if len(biases) != L:
+        raise ValueError('%d biases for %d layers' % (len(biases), L))
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        if w.ndim != 2 or not (1 <= w.shape[0] <= MAX_WIDTH and 1 <= w.shape[1] <= MAX_WIDTH):
+            raise ValueError('weights[%d] must be [out, in] with both in 1..%d, not %s' % (l, MAX_WIDTH, w.shape))
+        if l and w.shape[1] != weights[l - 1].shape[0]:
+            raise ValueError('weights[%d] takes %d inputs, layer %d has %d outputs' % (l, w.shape[1], l - 1, weights[l - 1].shape[0]))
+        if b is not None and b.shape != (w.shape[0],):
+            raise ValueError('biases[%d] must have shape (%d,), not %s' % (l, w.shape[0], b.shape))
+    if outputs is not None and weights[-1].shape[0] != outputs:
+        raise ValueError('the last layer must have %d output(s), not %d' % (outputs, weights[-1].shape[0]))
+    ptrs, d_w, d_b = [], [], []
+    for w, b in zip(weights, biases):
+        for a, out in ((w, d_w), (b, d_b)):
+            if a is None:
+                out.append(None)
+                continue
+            p = h.device_alloc(a.nbytes)
+            ptrs.append(p)
+            h.upload(p, a)
+            out.append(p)
+    return ptrs, [weights[0].shape[1]] + [w.shape[0] for w in weights], d_w, d_b
+
+
 class Actor:
     """``env.actor``: an MLP with ReLU hidden layers on the env's device, and the actions of the env's current rows."""
 
@@ -34,34 +67,10 @@ class Actor:
         of 1..256 units, each layer's inputs the outputs of the one before.  Replaces a network loaded earlier."""
         if out_activation not in ACTIVATIONS:
             raise ValueError('out_activation must be one of %s, not %r' % (sorted(ACTIVATIONS), out_activation))
-        weights = [np.ascontiguousarray(w, np.float32) for w in weights]
-        L = len(weights)
-        if not 1 <= L <= MAX_LAYERS:
-            raise ValueError('a network has 1..%d layers, not %d' % (MAX_LAYERS, L))
-        biases = [None] * L if biases is None else [None if b is None else np.ascontiguousarray(b, np.float32) for b in biases]
-        if len(biases) != L:
-            raise ValueError('%d biases for %d layers' % (len(biases), L))
-        for l, (w, b) in enumerate(zip(weights, biases)):
-            if w.ndim != 2 or not (1 <= w.shape[0] <= MAX_WIDTH and 1 <= w.shape[1] <= MAX_WIDTH):
-                raise ValueError('weights[%d] must be [out, in] with both in 1..%d, not %s' % (l, MAX_WIDTH, w.shape))
-            if l and w.shape[1] != weights[l - 1].shape[0]:
-                raise ValueError('weights[%d] takes %d inputs, layer %d has %d outputs' % (l, w.shape[1], l - 1, weights[l - 1].shape[0]))
-            if b is not None and b.shape != (w.shape[0],):
-                raise ValueError('biases[%d] must have shape (%d,), not %s' % (l, w.shape[0], b.shape))
+        loaded = upload_network(self._h, weights, biases)
         self.close()
-        h = self._h
-        d_w, d_b = [], []
-        for w, b in zip(weights, biases):
-            for a, out in ((w, d_w), (b, d_b)):
-                if a is None:
-                    out.append(None)
-                    continue
-                p = h.device_alloc(a.nbytes)
-                self._ptrs.append(p)
-                h.upload(p, a)
-                out.append(p)
-        self.widths = [weights[0].shape[1]] + [w.shape[0] for w in weights]
-        self._mlp = h.mlp_struct(self.widths, d_w, d_b, ACTIVATIONS[out_activation])
+        self._ptrs, self.widths, d_w, d_b = loaded
+        self._mlp = self._h.mlp_struct(self.widths, d_w, d_b, ACTIVATIONS[out_activation])
 
     def _loaded(self):
         if self._mlp is None:

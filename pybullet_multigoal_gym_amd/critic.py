@@ -1,0 +1,136 @@
+"""The critic of a goal-conditioned DDPG / HER learner on the device: Q(x, a) on two row tables read in place, and the TD target
+y = clip(r + gamma Q'(x', pi'(x'))) of a minibatch in one fused call.
+
+Host-side face of ``pmg_q_device`` and ``pmg_td_target_device`` (include/pmg.h), forward only.  All arithmetic happens
+in the HIP library; this file uploads the network, validates shapes and moves buffers.  The weights live in buffers this object owns
+until ``close()`` (or the next ``load``).  The update side of a device-resident learner starts with two stream-ordered calls:
+
+    env.critic.load(target_critic_weights, target_critic_biases)           # x_dim + a_dim -> ... -> 1
+    env.actor.load(target_actor_weights, target_actor_biases)              # an Actor holds any network: here the target actor
+    h.her_sample_device(rows, E, T, es, ts, B, ..., d_x_next=d_xn, d_reward=d_r, d_goal_achieved=d_ok)
+    env.critic.td_target_device(env.actor, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, d_terminal=d_ok, batch=B)
+"""
+import numpy as np
+
+from .actor import ACTIVATIONS, Actor, upload_network
+
+
+class Critic:
+    """``env.critic``: an MLP with ReLU hidden layers and one output on the env's device."""
+
+    def __init__(self, env):
+        self._env = env
+        self._h = env.handle
+        self._ptrs = []
+        self._mlp = None
+        self.widths = None
+
+    def load(self, weights, biases=None, out_activation='identity'):
+        """Upload a network as ``Actor.load`` does; the last layer must have one output.  Replaces a network loaded earlier."""
+        if out_activation not in ACTIVATIONS:
+            raise ValueError('out_activation must be one of %s, not %r' % (sorted(ACTIVATIONS), out_activation))
+        loaded = upload_network(self._h, weights, biases, outputs=1)
+        self.close()
+        self._ptrs, self.widths, d_w, d_b = loaded
+        self._mlp = self._h.mlp_struct(self.widths, d_w, d_b, ACTIVATIONS[out_activation])
+
+    def _loaded(self):
+        if self._mlp is None:
+            raise ValueError('no network: call load() first')
+        return self._mlp
+
+    def _target_actor(self, actor):
+        if not isinstance(actor, Actor):
+            raise ValueError('actor must be an Actor (whose loaded network is the target actor), not %r' % (type(actor),))
+        mlp = actor._loaded()
+        if actor.widths[0] + actor.widths[-1] != self.widths[0]:
+            raise ValueError('the actor maps %d -> %d, the critic takes %d inputs' % (actor.widths[0], actor.widths[-1], self.widths[0]))
+        return mlp
+
+    def q_device(self, d_x_ptr, x_dim, d_a_ptr, a_dim, batch, d_q_ptr, x_stride=None, a_stride=None, q_stride=1):
+        """d_q [batch] = Q(x, a) of the rows d_x [batch, x_dim] and d_a [batch, a_dim] in device memory (strides in floats, default:
+        contiguous); on the handle's stream, no host sync."""
+        self._h.q_device(self._loaded(), d_x_ptr, x_dim if x_stride is None else x_stride, x_dim, d_a_ptr, a_dim if a_stride is None else a_stride,
+                         a_dim, batch, d_q_ptr, q_stride)
+
+    def q(self, x, a):
+        """x [..., x_dim], a [..., a_dim] -> Q(x, a) [...] (numpy)."""
+        self._loaded()
+        h = self._h
+        x, a = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(a, np.float32)
+        if x.ndim == 0 or a.ndim == 0 or x.shape[:-1] != a.shape[:-1] or x.shape[-1] < 1 or a.shape[-1] < 1 or x.shape[-1] + a.shape[-1] != self.widths[0]:
+            raise ValueError('x %s / a %s must share their leading axes and their last axes sum to %d' % (x.shape, a.shape, self.widths[0]))
+        out = np.empty(x.shape[:-1], np.float32)
+        if out.size == 0:
+            return out
+        ptrs = []
+        try:
+            for arr in (x, a, out):
+                ptrs.append(h.device_alloc(arr.nbytes))
+            h.upload(ptrs[0], x)
+            h.upload(ptrs[1], a)
+            self.q_device(ptrs[0], x.shape[-1], ptrs[1], a.shape[-1], out.size, ptrs[2])
+            h.sync()
+            h.download(out, ptrs[2])
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+        return out
+
+    def td_target_device(self, actor, d_x_next, d_reward, d_y, gamma, clip_lo, clip_hi, d_terminal=None, d_q_next=None, d_next_action=None,
+                         x_stride=None, *, batch):
+        """d_y [batch] = clip(r + gamma Q'(x', pi'(x'))) with this network as Q' and ``actor``'s as pi', from d_x_next [batch, Dx] (x_stride
+        floats from row to row, default Dx) and d_reward [batch]; d_terminal [batch] uint8 (non-zero: y = clip(r)), d_q_next [batch] and
+        d_next_action [batch, A] are optional; clip_lo = -inf / clip_hi = inf: no clip.  On the handle's stream, no host sync."""
+        mlp = self._loaded()
+        amlp = self._target_actor(actor)
+        gamma, clip_lo, clip_hi = float(gamma), float(clip_lo), float(clip_hi)
+        if not gamma >= 0.0 or not np.isfinite(gamma):
+            raise ValueError('gamma %r must be finite and >= 0' % (gamma,))
+        if not clip_lo <= clip_hi:
+            raise ValueError('clips %r / %r must be ordered and not NaN' % (clip_lo, clip_hi))
+        h = self._h
+        td = h.td_struct(int(batch), d_x_next, actor.widths[0] if x_stride is None else x_stride, d_reward, d_y, gamma,
+                         clip_lo, clip_hi, d_terminal, d_q_next, d_next_action)
+        h.td_target_device(amlp, mlp, td)
+
+    def td_target(self, actor, x_next, reward, gamma, clip_lo=-float('inf'), clip_hi=float('inf'), terminal=None):
+        """x_next [B, Dx], reward [B], terminal [B] or None -> y [B], q_next [B], next_action [B, A] (numpy)."""
+        self._loaded()
+        self._target_actor(actor)
+        h = self._h
+        Dx, A = actor.widths[0], actor.widths[-1]
+        x_next, reward = np.ascontiguousarray(x_next, np.float32), np.ascontiguousarray(reward, np.float32)
+        if x_next.ndim != 2 or x_next.shape[1] != Dx or reward.shape != (x_next.shape[0],):
+            raise ValueError('x_next %s must be [B, %d] and reward %s [B]' % (x_next.shape, Dx, reward.shape))
+        B = x_next.shape[0]
+        if terminal is not None:
+            terminal = np.ascontiguousarray(np.asarray(terminal) != 0, np.uint8)
+            if terminal.shape != (B,):
+                raise ValueError('terminal %s must be [B]' % (terminal.shape,))
+        y, qn, na = np.empty(B, np.float32), np.empty(B, np.float32), np.empty((B, A), np.float32)
+        if B == 0:
+            return y, qn, na
+        ins = [x_next, reward] + ([terminal] if terminal is not None else [])
+        ptrs = []
+        try:
+            for arr in ins + [y, qn, na]:
+                ptrs.append(h.device_alloc(arr.nbytes))
+            for p, arr in zip(ptrs, ins):
+                h.upload(p, arr)
+            d_y, d_qn, d_na = ptrs[len(ins):]
+            self.td_target_device(actor, ptrs[0], ptrs[1], d_y, gamma, clip_lo, clip_hi, ptrs[2] if terminal is not None else None, d_qn, d_na, batch=B)
+            h.sync()
+            for arr, p in ((y, d_y), (qn, d_qn), (na, d_na)):
+                h.download(arr, p)
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+        return y, qn, na
+
+    def close(self):
+        """Free the uploaded network."""
+        if getattr(self._h, 'h', None):
+            for p in self._ptrs:
+                self._h.device_free(p)
+        self._ptrs, self._mlp, self.widths = [], None, None

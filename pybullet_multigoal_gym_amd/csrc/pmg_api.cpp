@@ -1018,6 +1018,63 @@ int pmg_act_env_device(pmg_env* e, const pmg_mlp* mlp, int state_kind, const pmg
     return PMG_OK;
 }
 
+/* ---- critic and TD target ---- */
+/* a critic takes in_dim inputs and has one output; 0 or PMG_E_INVALID */
+static int critic_of(pmg_env* e, const PmgMlp& M, int in_dim, const char* who)
+{
+    if (M.width[0] != in_dim || M.width[M.L] != 1)
+        return fail(e, PMG_E_INVALID, "%s: the critic maps %d -> %d, the rows need %d -> 1", who, M.width[0], M.width[M.L], in_dim);
+    return PMG_OK;
+}
+
+int pmg_q_device(pmg_env* e, const pmg_mlp* critic, const float* d_x, int64_t x_stride, int32_t x_dim, const float* d_a, int64_t a_stride,
+                 int32_t a_dim, int64_t batch, float* d_q, int64_t q_stride)
+{
+    if (!e) return PMG_E_INVALID;
+    PmgMlp M;
+    if (int rc = mlp_of(e, critic, "pmg_q_device", M)) return rc;
+    if (x_dim < 1 || a_dim < 1 || x_dim > 256 || a_dim > 256) return fail(e, PMG_E_INVALID, "pmg_q_device: x_dim %d / a_dim %d must be >= 1 (and sum to at most 256)", x_dim, a_dim);
+    if (int rc = critic_of(e, M, x_dim + a_dim, "pmg_q_device")) return rc;
+    if (!d_x || !d_a || !d_q) return fail(e, PMG_E_INVALID, "pmg_q_device: null pointer");
+    if ((((size_t)d_x | (size_t)d_a | (size_t)d_q) & 3) != 0) return fail(e, PMG_E_INVALID, "pmg_q_device: a row pointer is not aligned to 4 bytes");
+    if (batch < 0) return fail(e, PMG_E_INVALID, "pmg_q_device: batch %lld is negative", (long long)batch);
+    if (x_stride < x_dim || a_stride < a_dim || q_stride < 1)
+        return fail(e, PMG_E_INVALID, "pmg_q_device: strides %lld / %lld / %lld are smaller than the widths %d / %d / 1", (long long)x_stride, (long long)a_stride, (long long)q_stride, x_dim, a_dim);
+    if (batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = batch; M.out = d_q; M.out_stride = q_stride;
+    HIP_TRY(e, pmg_launch_mlp_q(M, d_x, x_stride, x_dim, d_a, a_stride, e->stream));
+    return PMG_OK;
+}
+
+int pmg_td_target_device(pmg_env* e, const pmg_mlp* actor_target, const pmg_mlp* critic_target, const pmg_td_target* td)
+{
+    if (!e) return PMG_E_INVALID;
+    PmgMlp P, Q;
+    if (int rc = mlp_of(e, actor_target, "pmg_td_target_device (actor)", P)) return rc;
+    if (int rc = mlp_of(e, critic_target, "pmg_td_target_device (critic)", Q)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L];
+    if (int rc = critic_of(e, Q, Dx + A, "pmg_td_target_device")) return rc;
+    if (!td) return fail(e, PMG_E_INVALID, "pmg_td_target_device: td is null");
+    if (td->struct_size != (int32_t)sizeof(pmg_td_target)) return fail(e, PMG_E_INVALID, "pmg_td_target_device: struct_size %d != %zu", td->struct_size, sizeof(pmg_td_target));
+    if (!td->d_x_next || !td->d_reward || !td->d_y) return fail(e, PMG_E_INVALID, "pmg_td_target_device: d_x_next, d_reward or d_y is null");
+    if ((((size_t)td->d_x_next | (size_t)td->d_reward | (size_t)td->d_y | (size_t)td->d_q_next | (size_t)td->d_next_action) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "pmg_td_target_device: a float pointer is not aligned to 4 bytes");
+    if (td->batch < 0) return fail(e, PMG_E_INVALID, "pmg_td_target_device: batch %lld is negative", (long long)td->batch);
+    if (td->x_stride < Dx) return fail(e, PMG_E_INVALID, "pmg_td_target_device: x_stride %lld is smaller than the width %d", (long long)td->x_stride, Dx);
+    if (!(td->gamma >= 0.f) || std::isinf(td->gamma)) return fail(e, PMG_E_INVALID, "pmg_td_target_device: gamma %g must be finite and >= 0", (double)td->gamma);
+    if (!(td->clip_lo <= td->clip_hi)) return fail(e, PMG_E_INVALID, "pmg_td_target_device: clips %g / %g must be ordered and not NaN", (double)td->clip_lo, (double)td->clip_hi);
+    if (td->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = Q.B = td->batch;
+    PmgTd T;
+    T.xn = td->d_x_next; T.xs = td->x_stride; T.reward = td->d_reward; T.term = td->d_terminal;
+    T.gamma = td->gamma; T.lo = td->clip_lo; T.hi = td->clip_hi;
+    T.y = td->d_y; T.qn = td->d_q_next; T.na = td->d_next_action;
+    HIP_TRY(e, pmg_launch_td_target(P, Q, T, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

@@ -69,4 +69,16 @@ struct PmgMlpEnv {
 };
 hipError_t pmg_launch_mlp_forward(const PmgMlp& M, const float* d_in, long long in_stride, hipStream_t s);
 hipError_t pmg_launch_mlp_act(const PmgMlp& M, const PmgMlpEnv& E, hipStream_t s);
+
+/* critic and TD target (pmg_q_device, pmg_td_target_device), validated by the caller.  q: M = the critic (width[L] == 1) with
+ * out = d_q, on the rows x[r] | a[r] (x_dim | width[0] - x_dim floats).  TD target: actor.B rows of x' [B, actor.width[0]] at xs floats, the
+ * critic takes actor.width[0] + actor.width[L] inputs; term, qn, na may be null; na is [B, actor.width[L]] contiguous. */
+struct PmgTd {
+    const float* xn; long long xs;
+    const float* reward; const unsigned char* term;
+    float gamma, lo, hi;
+    float* y; float* qn; float* na;
+};
+hipError_t pmg_launch_mlp_q(const PmgMlp& M, const float* d_x, long long x_stride, int x_dim, const float* d_a, long long a_stride, hipStream_t s);
+hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const PmgTd& T, hipStream_t s);
 #endif

@@ -1,6 +1,7 @@
 /* pmg_learner_body.inc -- the learner-side kernels and their launchers (included by pmg_kernels.hip): rewards of [B, G] batches,
- * the running normaliser, policy-input rows, HER minibatches and the actor forward (DESIGN.md 3.6-3.9).  None of them touches EnvParams.  What two
- * kernels share has ONE definition, so that they agree bit for bit by construction: reward_of, sq_dist, policy_norm, flat_sweep. */
+ * the running normaliser, policy-input rows, HER minibatches, the actor forward and the critic / TD target (DESIGN.md 3.6-3.10).  None of them
+ * touches EnvParams.  What two kernels share has ONE definition, so that they agree bit for bit by construction: reward_of, sq_dist,
+ * policy_norm, flat_sweep, mlp_gather, mlp_layers. */
 /* distance, threshold, binary -> reward value and flag: the one definition (all three reward kernels and pmg_k_her_draw) */
 __device__ __forceinline__ float reward_of(float d, float thr, int binary, unsigned char& ok)
 {
@@ -527,11 +528,18 @@ struct MlpEnvRows {
         return policy_norm(E.rows[r * E.stride + (st ? E.so : E.dgo) + c], der[c], der[2 * D + c], E.cin, E.cout);
     }
 };
+/* the row x[r] | a[r] of two tables read in place (pmg_q_device): columns below Dx from x, the others from a */
+struct MlpCatRows {
+    const float* __restrict__ x; long long xs; const float* __restrict__ a; long long as; int Dx;
+    __device__ __forceinline__ float at(long long r, int col) const { return col < Dx ? x[r * xs + col] : a[r * as + (col - Dx)]; }
+};
+/* pre-activation z -> the action without exploration: clip(out_activation(z)) (mlp_action, and a' of pmg_k_td_target) */
+__device__ __forceinline__ float mlp_plain_action(int out_act, float z) { return fminf(fmaxf(out_act ? tanhf(z) : z, -1.f), 1.f); }
 /* pre-activation z of column j of global env g -> action (include/pmg.h): HER's generator with b = g A + j as the sample index */
 __device__ __forceinline__ float mlp_action(const PmgMlp& M, float z, unsigned long long g, int j, int A)
 {
+    if (!M.explore) return mlp_plain_action(M.out_act, z);
     float a = M.out_act ? tanhf(z) : z;
-    if (!M.explore) return fminf(fmaxf(a, -1.f), 1.f);
     const unsigned long long z0 = M.key + (4ull * (g * (unsigned long long)A) + 1ull) * HER_GOLD;   /* column 0 of the env */
     const unsigned long long zb = z0 + 4ull * (unsigned long long)j * HER_GOLD;
     if (M.noise_eps > 0.f) {
@@ -546,6 +554,50 @@ __device__ __forceinline__ float mlp_action(const PmgMlp& M, float z, unsigned l
     }
     return a;
 }
+/* columns [0, K) of the 32 rows from row0 of a row source into the tile, lanes along the columns; rows past the batch and the columns
+ * [K, Kp) (Kp = K rounded up to even: the padding column of an odd K; Kp = K: none) are written as zeros.  Every address is valid
+ * (clamped), so the loads of a thread are in flight together */
+template <class Src>
+__device__ __forceinline__ void mlp_gather(float* tile, const Src& S, long long row0, long long B, int K, int Kp, int t)
+{
+#pragma unroll 4
+    for (int i = t; i < MLP_ROWS * Kp; i += 256) {
+        const int r = i / Kp, c = i - r * Kp;
+        const bool in = row0 + r < B && c < K;
+        tile[r * MLP_LD + c] = mlp_keep(S.at(row0 + r < B ? row0 + r : B - 1, c < K ? c : K - 1), in);
+    }
+}
+/* THE layer loop (every instantiation of pmg_k_mlp and both networks of pmg_k_td_target): all layers of M on the tile, whose columns
+ * [0, width[0] rounded up to even) hold the input and real zeros as padding; behind the closing barrier columns [0, width[L]) hold z */
+__device__ __forceinline__ void mlp_layers(float* tile, const PmgMlp& M, int lane, int wave, int col)
+{
+#pragma unroll 1
+    for (int l = 0; l < M.L; l++) {
+        const int K = M.width[l], Nn = M.width[l + 1];
+        const float* __restrict__ W = M.w[l];
+        const float* __restrict__ bias = M.b[l];
+        const int u0 = 32 * wave + col, u1 = u0 + 128;            /* this lane's unit in the strips wave and wave + 4 */
+        const bool live0 = u0 < Nn, live1 = u1 < Nn, strip0 = 32 * wave < Nn, strip1 = 32 * wave + 128 < Nn;
+        /* a unit past the width runs on row 0 of W: valid addresses, results never used */
+        const float* w0 = W + (long long)(live0 ? u0 : 0) * K;
+        const float* w1 = W + (long long)(live1 ? u1 : 0) * K;
+        const float b0 = bias ? bias[live0 ? u0 : 0] : 0.f, b1 = bias ? bias[live1 ? u1 : 0] : 0.f;
+        MlpAcc acc0, acc1;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { acc0[reg] = b0; acc1[reg] = b1; }
+        if (strip1) mlp_chain<2>(tile, w0, w1, K, lane, acc0, acc1);
+        else if (strip0) mlp_chain<1>(tile, w0, w1, K, lane, acc0, acc1);
+        const bool hidden = l + 1 < M.L;
+        __syncthreads();                                         /* every wavefront has read the layer's input */
+        /* whole strips: a unit past the width becomes +0.0, the next layer's padding */
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            if (strip0) tile[mlp_row(reg, lane) * MLP_LD + u0] = live0 ? (hidden ? fmaxf(acc0[reg], 0.f) : acc0[reg]) : 0.f;
+            if (strip1) tile[mlp_row(reg, lane) * MLP_LD + u1] = live1 ? (hidden ? fmaxf(acc1[reg], 0.f) : acc1[reg]) : 0.f;
+        }
+        __syncthreads();
+    }
+}
 template <class Src, bool ACT>
 __global__ void __launch_bounds__(256) pmg_k_mlp(Src S, PmgMlp M)
 {
@@ -554,43 +606,9 @@ __global__ void __launch_bounds__(256) pmg_k_mlp(Src S, PmgMlp M)
     const long long ntiles = (M.B + MLP_ROWS - 1) / MLP_ROWS;
     for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
         const long long row0 = tb * MLP_ROWS;
-        {   /* the input rows, lanes along the columns; rows past the batch and column K of an odd K: zeros.  Every address is valid
-             * (clamped), so the loads of a thread are in flight together */
-            const int K = M.width[0], Kp = (K + 1) & ~1;
-#pragma unroll 4
-            for (int i = t; i < MLP_ROWS * Kp; i += 256) {
-                const int r = i / Kp, c = i - r * Kp;
-                const bool in = row0 + r < M.B && c < K;
-                tile[r * MLP_LD + c] = mlp_keep(S.at(row0 + r < M.B ? row0 + r : M.B - 1, c < K ? c : K - 1), in);
-            }
-        }
+        mlp_gather(tile, S, row0, M.B, M.width[0], (M.width[0] + 1) & ~1, t);
         __syncthreads();
-#pragma unroll 1
-        for (int l = 0; l < M.L; l++) {
-            const int K = M.width[l], Nn = M.width[l + 1];
-            const float* __restrict__ W = M.w[l];
-            const float* __restrict__ bias = M.b[l];
-            const int u0 = 32 * wave + col, u1 = u0 + 128;            /* this lane's unit in the strips wave and wave + 4 */
-            const bool live0 = u0 < Nn, live1 = u1 < Nn, strip0 = 32 * wave < Nn, strip1 = 32 * wave + 128 < Nn;
-            /* a unit past the width runs on row 0 of W: valid addresses, results never used */
-            const float* w0 = W + (long long)(live0 ? u0 : 0) * K;
-            const float* w1 = W + (long long)(live1 ? u1 : 0) * K;
-            const float b0 = bias ? bias[live0 ? u0 : 0] : 0.f, b1 = bias ? bias[live1 ? u1 : 0] : 0.f;
-            MlpAcc acc0, acc1;
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) { acc0[reg] = b0; acc1[reg] = b1; }
-            if (strip1) mlp_chain<2>(tile, w0, w1, K, lane, acc0, acc1);
-            else if (strip0) mlp_chain<1>(tile, w0, w1, K, lane, acc0, acc1);
-            const bool hidden = l + 1 < M.L;
-            __syncthreads();                                         /* every wavefront has read the layer's input */
-            /* whole strips: a unit past the width becomes +0.0, the next layer's padding */
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                if (strip0) tile[mlp_row(reg, lane) * MLP_LD + u0] = live0 ? (hidden ? fmaxf(acc0[reg], 0.f) : acc0[reg]) : 0.f;
-                if (strip1) tile[mlp_row(reg, lane) * MLP_LD + u1] = live1 ? (hidden ? fmaxf(acc1[reg], 0.f) : acc1[reg]) : 0.f;
-            }
-            __syncthreads();
-        }
+        mlp_layers(tile, M, lane, wave, col);
         {   /* the tile holds z: thread per (row, unit), units along the lanes */
             const int A = M.width[M.L];
             for (int i = t; i < MLP_ROWS * A; i += 256) {
@@ -604,6 +622,53 @@ __global__ void __launch_bounds__(256) pmg_k_mlp(Src S, PmgMlp M)
                 } else
                     M.out[row * M.out_stride + j] = M.out_act ? tanhf(z) : z;
             }
+        }
+        __syncthreads();                                             /* the next tile's rows overwrite this one's */
+    }
+}
+/* TD target of DDPG / HER (pmg_td_target_device, DESIGN.md 3.10): y = clip(r + gamma Q'(x', pi'(x'))), both networks on ONE tile.  After the
+ * actor's layers z sits in columns [0, A); a' = mlp_plain_action(z) moves to columns [Dx, Dx + A), the critic's action columns.  Source and
+ * target overlap when A > Dx, so a thread per (row, unit) carries its value in a register across a barrier, eight units of all 32 rows per
+ * pass, the units in DESCENDING order: a pass writes only columns above every column a later pass reads.  Then columns [0, Dx) are
+ * gathered again from x' (layer 0 of the actor overwrote them; L2-resident) and column Dx + A of an odd Dx + A becomes +0.0.  Every
+ * column the critic's layer 0 reads is thereby written for all 32 rows behind the actor -- rows past the batch as zeros --, so no stale
+ * hidden activation (which may be inf) meets a padding zero.  A thread per row forms y from the critic's single output column. */
+__global__ void __launch_bounds__(256) pmg_k_td_target(PmgMlp P, PmgMlp Q, PmgTd T)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L];
+    const MlpRawRows S = {T.xn, T.xs};
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        mlp_layers(tile, P, lane, wave, col);
+        {
+            const int r = t >> 3;
+            const long long row = row0 + r;
+            for (int hi = A; hi > 0; hi -= 8) {
+                const int j = hi - 8 + (t & 7);                      /* units [hi - 8, hi) of the 32 rows */
+                const float z = j >= 0 ? tile[r * MLP_LD + j] : 0.f;
+                __syncthreads();                                     /* the pass has read its z: columns [Dx + hi - 8, Dx + hi) are free */
+                if (j >= 0) {
+                    const float a = mlp_plain_action(P.out_act, z);
+                    tile[r * MLP_LD + Dx + j] = row < P.B ? a : 0.f;
+                    if (T.na && row < P.B) T.na[row * A + j] = a;
+                }
+            }
+        }
+        mlp_gather(tile, S, row0, P.B, Dx, Dx, t);                   /* columns below Dx: no pass wrote them, every pass is done reading */
+        if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+        __syncthreads();
+        mlp_layers(tile, Q, lane, wave, col);
+        if (t < MLP_ROWS && row0 + t < P.B) {
+            const long long row = row0 + t;
+            const float z = tile[t * MLP_LD], q = Q.out_act ? tanhf(z) : z, r = T.reward[row];
+            const float v = T.term && T.term[row] ? r : fmaf(T.gamma, q, r);
+            T.y[row] = fminf(fmaxf(v, T.lo), T.hi);
+            if (T.qn) T.qn[row] = q;
         }
         __syncthreads();                                             /* the next tile's rows overwrite this one's */
     }
@@ -627,5 +692,18 @@ hipError_t pmg_launch_mlp_act(const PmgMlp& net, const PmgMlpEnv& E, hipStream_t
     M.key = her_mix(M.seed ^ her_mix(M.counter + HER_GOLD));
     const MlpEnvRows S = {E};
     hipLaunchKernelGGL((pmg_k_mlp<MlpEnvRows, true>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_mlp_q(const PmgMlp& M, const float* d_x, long long x_stride, int x_dim, const float* d_a, long long a_stride, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    const MlpCatRows S = {d_x, x_stride, d_a, a_stride, x_dim};
+    hipLaunchKernelGGL((pmg_k_mlp<MlpCatRows, false>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const PmgTd& T, hipStream_t s)
+{
+    if (actor.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pmg_k_td_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic, T);
     return hipGetLastError();
 }

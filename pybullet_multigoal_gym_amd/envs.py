@@ -294,10 +294,21 @@ class KukaVecEnv:
             self._actor = Actor(self)
         return self._actor
 
+    @property
+    def critic(self):
+        """The critic network of this env's learner on the device (critic.Critic): Q(x, a) and fused TD targets, created on first
+        access."""
+        if getattr(self, '_critic', None) is None:
+            from .critic import Critic
+            self._critic = Critic(self)
+        return self._critic
+
     def close(self):
         if not self._closed:
             if getattr(self, '_actor', None) is not None:
                 self._actor.close()
+            if getattr(self, '_critic', None) is not None:
+                self._critic.close()
             self.handle.close()
             self._closed = True
 
