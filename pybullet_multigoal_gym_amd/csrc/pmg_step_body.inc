@@ -1194,7 +1194,13 @@ __device__ __forceinline__ bool substep(const EnvParams& P, ContactLds<NB, MAXC>
      * (zero for the isotropic cubes, not for the slide puck) */
     if (l < nb) {
         float* b = L.blk[l];
-        const float* Rm = L.blkR[l];
+        /* the puck's rotation for the gyroscopic term.  Two-wavefront workgroups: L.blkR is the HELPER's, written behind barrier A
+         * (publish_frames) for its narrowphase, and nothing orders that write against a read here, in front of barrier B -- this
+         * wavefront takes the rotation from the quaternion itself, which nobody writes between A and B (the same quat_to_R on the same
+         * numbers: the helper's bits).  tests/test_wave_order.py */
+        float Rown[9];
+        if (TWO && ObjT<CYL>::cyl) quat_to_R(b + 3, Rown);
+        const float* Rm = (TWO && ObjT<CYL>::cyl) ? Rown : L.blkR[l];
         float kl = LINK_DAMPING * (1.f + sqrtf(dot3(b + 7, b + 7))), ka = LINK_DAMPING * (1.f + sqrtf(dot3(b + 10, b + 10)));
         float al[3] = {-b[10] * ka, -b[11] * ka, -b[12] * ka};
         if (ObjT<CYL>::cyl) {

@@ -63,6 +63,30 @@ std::vector<Fiber> g_fibers;
 int g_cur = -1;
 const std::function<void()>* g_body = nullptr;
 int g_bar_gen = 0, g_bar_count = 0, g_live = 0;   /* workgroup barrier: generation, arrivals, live threads */
+/* Wavefront-order policy (pmge_set_wave_order): empty = the default scheduler below, every live fiber one yield per pass */
+constexpr int MAX_WAVES = 16;
+int g_order[MAX_WAVES], g_norder = 0;
+long long g_order_launches = 0;
+
+inline bool runnable(const Fiber& f) { return !f.done && !(f.wait_gen >= 0 && f.wait_gen == g_bar_gen); }
+/* the first wavefront of the priority list (the named ones, then the others in index order) that has a runnable fiber; -1: none */
+int pick_wave(int block)
+{
+    const int nw = (block + 63) / 64;
+    int seq[2 * MAX_WAVES], n = 0;
+    for (int o = 0; o < g_norder; o++) seq[n++] = g_order[o];
+    for (int w = 0; w < nw && w < MAX_WAVES; w++) {
+        bool named = false;
+        for (int o = 0; o < g_norder; o++) named |= g_order[o] == w;
+        if (!named) seq[n++] = w;
+    }
+    for (int k = 0; k < n; k++) {
+        const int w = seq[k];
+        for (int i = 64 * w; i < block && i < 64 * w + 64; i++)
+            if (runnable(g_fibers[i])) return w;
+    }
+    return -1;
+}
 
 void trampoline()
 {
@@ -103,6 +127,23 @@ void emu_barrier()
 #endif
 }
 
+/* Wavefront order of every later launch (test_wave_order.py).  With n > 0 the scheduler runs ONE wavefront per pass: the first in
+ * `order` (wavefront = threadIdx.x >> 6; the ones not named follow in index order) that has a runnable fiber -- so a wavefront runs
+ * from one workgroup barrier to its next, or to its end, before any wavefront behind it in the list moves.  Two accesses of two
+ * wavefronts to one LDS word that no barrier orders thus happen in the list's order: identity and reverse together put either one
+ * first.  n == 0: the default scheduler.  Entries outside 0..15 and repeats are dropped */
+extern "C" void pmge_set_wave_order(const int* order, int n)
+{
+    g_norder = 0;
+    for (int o = 0; o < n && g_norder < MAX_WAVES; o++) {
+        bool ok = order[o] >= 0 && order[o] < MAX_WAVES;
+        for (int k = 0; k < g_norder; k++) ok &= g_order[k] != order[o];
+        if (ok) g_order[g_norder++] = order[o];
+    }
+}
+/* workgroups of more than one wavefront that ran under a non-empty order since load */
+extern "C" long long pmge_wave_order_launches() { return g_order_launches; }
+
 void emu::launch(int grid, int block, const std::function<void()>& body)
 {
     g_body = &body;
@@ -134,11 +175,15 @@ void emu::launch(int grid, int block, const std::function<void()>& body)
 #endif
         }
         g_live = block; g_bar_count = 0;
+        const bool ordered = g_norder > 0 && block > 64 && block <= 64 * MAX_WAVES;
+        if (ordered) g_order_launches++;
         bool alive = true;
         while (alive) {
             alive = false;
+            const int pick = ordered ? pick_wave(block) : -1;
             for (int i = 0; i < block; i++) {
                 if (g_fibers[i].done) continue;
+                if (pick >= 0 && (i >> 6) != pick) { alive = true; continue; }   /* another wavefront's turn */
                 if (g_fibers[i].wait_gen >= 0 && g_fibers[i].wait_gen == g_bar_gen) { alive = true; continue; }   /* parked */
                 g_cur = i;
                 threadIdx = {(unsigned)i, 0, 0};

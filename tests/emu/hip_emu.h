@@ -11,6 +11,12 @@
  * "yield until everybody arrived" barrier, so the semantics are those of a
  * lock-step wavefront as long as cross-lane ops are called convergently
  * (which the GPU requires anyway).
+ *
+ * Scheduling.  By default every pass resumes every live fiber once, in index order: between two workgroup barriers the
+ * wavefronts of a workgroup interleave in ONE fixed way.  pmge_set_wave_order() replaces that by a priority list of
+ * wavefronts: a pass resumes the fibers of one wavefront only, the first in the list that can run, so each wavefront
+ * runs from barrier to barrier ahead of the ones behind it.  An LDS hand-over between wavefronts that no barrier orders
+ * gives different results under the identity and the reverse list (tests/test_wave_order.py).
  */
 #ifndef PMG_HIP_EMU_H
 #define PMG_HIP_EMU_H
@@ -48,6 +54,9 @@ void emu_block_barrier();   /* workgroup-level: every live thread arrives */
 extern float emu_xf[16 * 64 * 16]; /* [wave][slot][lane] */
 extern long long pmge_face_clip_calls;   /* calls of box_face_clip (pmg_contact_body.inc) since load */
 extern long long pmge_cyl_contact_calls, pmge_cyl_redo_calls, pmge_cyl_spec_taken_n;   /* cylinder pairs found in contact by the float pass / repeated in double (cyl_redo64) */
+
+extern "C" void pmge_set_wave_order(const int* order, int n);   /* n == 0: the default scheduler */
+extern "C" long long pmge_wave_order_launches();                /* workgroups of several wavefronts run under an order */
 
 namespace emu {
 void launch(int grid, int block, const std::function<void()>& body);

@@ -184,3 +184,25 @@ extern "C" int pmge_probe_plan(int n_envs, int nb, const float* hot, const float
     memcpy(sched_out, sc.data(), sizeof(int) * (size_t)(P.schedule().wg_counts() - sc.data()));   /* counts, lists, redo count and list */
     return P.schedule().promoted();                         /* 0 / 1: the word pmg_k_step_list reads for its issue priority */
 }
+
+/* The wavefront-order detector's own probes (tests/test_wave_order.py; emulator only): 128 threads, wavefront 1 hands one LDS word to
+ * wavefront 0 between two workgroup barriers.  _racy: nothing orders the write and the read -- what wavefront 0 sees depends on
+ * which wavefront runs first, and the orders 01 and 10 must tell.  _fenced: a barrier between them -- every order agrees.
+ * out[0]: the word wavefront 0 read (7 = the initial value, 42 = wavefront 1's) */
+static void probe_handover(bool fenced, int* out)
+{
+    emu::launch(1, 128, [&]() {
+        __shared__ int word;
+        const int t = (int)threadIdx.x, w = t >> 6;
+        if (t == 0) word = 7;
+        __syncthreads();
+        if (w == 1 && (t & 63) == 0) word = 42;
+        if (fenced) __syncthreads();
+        int seen = 0;
+        if (w == 0) seen = word;
+        __syncthreads();
+        if (t == 0) out[0] = seen;
+    });
+}
+extern "C" void pmge_probe_handover_racy(int* out) { probe_handover(false, out); }
+extern "C" void pmge_probe_handover_fenced(int* out) { probe_handover(true, out); }
