@@ -252,7 +252,7 @@ int pmg_her_sample_device(pmg_env* env, const pmg_her_source* src, const pmg_her
 /* The actor on the device: a multi-layer perceptron on rows of floats, and the exploration policy of DDPG / HER on its output (no
  * reference equivalent: the reference leaves the policy to its caller).  With it a rollout is two stream-ordered calls per step,
  * pmg_act_env_device and pmg_step_device, and nothing leaves the GPU.  The caller owns the weights (device memory, read in place,
- * never written); the library keeps no learner state.  Both calls are stream-ordered on the handle's stream, sync nothing, write
+ * never written by these two calls; the update side below writes only what it is handed); the library keeps no learner state.  Both calls are stream-ordered on the handle's stream, sync nothing, write
  * only their outputs and touch no state of the handle: state rows, packed rows, RNG streams and normaliser totals stay as they are.
  *
  * Layers (normative).  Layer l, row r, unit j is ONE float32 chain: acc = bias[j] (+0.0 without a bias), then
@@ -299,8 +299,8 @@ int pmg_act_env_device(pmg_env* env, const pmg_mlp* mlp, int state_kind, const p
 
 /* The critic Q(x, a) and the TD target of a DDPG / HER update on the device, forward only (no reference equivalent).  Both entries
  * take networks as pmg_mlp above, are stream-ordered on the handle's stream, sync nothing, write only their outputs and touch no
- * state of the handle.  The learner loop is pmg_her_sample_device -> pmg_td_target_device on its d_x_next and d_reward; gradients
- * and optimiser steps are the caller's.
+ * state of the handle.  The learner loop is pmg_her_sample_device -> pmg_td_target_device on its d_x_next and d_reward -> the
+ * gradients, Adam steps and Polyak updates of pmg_mlp_grad_device, pmg_mlp_adam_device and pmg_mlp_polyak_device below.
  *
  * pmg_q_device: q[b] (at d_q + b * q_stride) = out_activation(z) of the critic on the row x[b] | a[b]: column c < x_dim is
  * x[b][c], column x_dim + j is a[b][j]; both tables are read in place at their own strides.  It is the layer chain above on that
@@ -333,6 +333,73 @@ typedef struct pmg_td_target {
     float* d_next_action;                /* [B, A]  or NULL: a' */
 } pmg_td_target;
 int pmg_td_target_device(pmg_env* env, const pmg_mlp* actor_target, const pmg_mlp* critic_target, const pmg_td_target* td);
+
+/* The update side of a DDPG / HER learner on the device (no reference equivalent): back-propagation through a pmg_mlp, an Adam step and
+ * a Polyak (soft target) update.  All three are stream-ordered on the handle's stream, sync nothing, write only their outputs (and
+ * d_work) and touch no state of the handle.
+ *
+ * pmg_mlp_grad_device (normative), float32 throughout.
+ * Forward: the layer chain above, unchanged.  h_0 is the input row (with d_a: the row x[b] | a[b] as in pmg_q_device), z_l[j] the fmaf
+ * chain over k ascending from bias[j], h_{l+1} = fmaxf(z_l, 0) on hidden layers, o = out_activation ? tanhf(z_{L-1}) : z_{L-1}.  d_out,
+ * when given, receives o.
+ * Head: g[b][j] = d_gout[b][j] when d_gout is given;  gscale * (o[b][j] - d_target[b][j]) (two roundings) when d_gout is NULL and
+ * d_target is given -- the MSE of a critic with gscale = 2 / B;  the constant gscale when both are NULL -- the actor's -mean Q with
+ * gscale = -1 / B.  Giving both is invalid.
+ * Output delta: delta_{L-1} = out_activation ? g * fmaf(-o, o, 1.f) : g, with o the very value written to d_out.
+ * Backward, l = L-1 ... 0:
+ *   dW_l[j][k]: acc = +0.0; acc = fmaf(delta_l[b][j], h_l[b][k], acc) for b = 0 ... B-1 ascending: ONE chain, no split over the batch.
+ *   db_l[j]:    acc = +0.0; acc = acc + delta_l[b][j] for b ascending (fmaf(delta, 1, acc) is the same value).
+ *   s_l[b][k]:  acc = +0.0; acc = fmaf(delta_l[b][j], W_l[j][k], acc) for j = 0 ... width[l+1]-1 ascending.
+ *     l >= 1: delta_{l-1}[b][k] = h_l[b][k] > 0 ? s_l[b][k] : +0.0 -- a real +0.0, not a product with a zero, so a masked inf does not
+ *             become a NaN; a unit whose z is exactly 0 is masked.
+ *     l == 0: s_0[b][c] goes to d_gx[b][c] for c < x_dim and to d_ga[b][c - x_dim] otherwise.
+ * As in the forward, padding products of exact zeros may follow a chain: they affect only the sign of a zero.
+ * A row's delta, d_gx, d_ga and d_out do not depend on the batch it is in; dW and db depend on the row order and on nothing else; nothing
+ * depends on the grid or the number of compute units; two calls on the same inputs give the same bits.
+ * Known limit: the single chain over the batch costs B / 2 dependent matrix steps per tile of a dW.  That is the right trade for the
+ * minibatches HER uses (256 to 4096 rows); a chunked reduction with its own normative order is later work.
+ *
+ * PMG_E_INVALID, with nothing launched: everything pmg_q_device rejects in the network and the row tables; d_a without a_dim >= 1 or the
+ * reverse; x_dim + a_dim != width[0]; d_ga without d_a; both d_gout and d_target; gscale not finite; grads, d_gx, d_ga and d_out all
+ * NULL; a grads tensor that is NULL where the network has that tensor, or a bias gradient where it has no bias; d_work NULL or
+ * work_floats too small; a float pointer off 4 bytes; a stride below its width; batch < 0; a wrong struct_size.  batch == 0 is a
+ * successful no-op that leaves grads untouched. */
+typedef struct pmg_mlp_params {          /* one float per parameter, pmg_mlp's layout: [width[l + 1], width[l]] and [width[l + 1]] */
+    float* d_weight[4];
+    float* d_bias[4];                    /* NULL where the network has no bias */
+} pmg_mlp_params;
+typedef struct pmg_mlp_grad {
+    int32_t struct_size, reserved;
+    float gscale;                        /* finite */
+    int32_t x_dim, a_dim;                /* a_dim == 0 with d_a == NULL: raw rows, x_dim == width[0] */
+    int32_t reserved2;
+    int64_t batch;
+    const float* d_x; int64_t x_stride;            /* rows; with d_a: the row x[b] | a[b] as in pmg_q_device */
+    const float* d_a; int64_t a_stride;            /* or NULL */
+    const float* d_gout; int64_t gout_stride;      /* [B, width[L]] dLoss / d out, or NULL (see the head) */
+    const float* d_target; int64_t target_stride;  /* [B, width[L]] or NULL */
+    const pmg_mlp_params* grads;         /* written (overwritten, never accumulated into); NULL = input gradients only */
+    float* d_gx; int64_t gx_stride;      /* [B, x_dim] or NULL */
+    float* d_ga; int64_t ga_stride;      /* [B, a_dim] or NULL */
+    float* d_out; int64_t out_stride;    /* [B, width[L]] or NULL: out_activation(z), the forward's result */
+    float* d_work; int64_t work_floats;  /* scratch, at least pmg_mlp_grad_work_floats(mlp, batch) */
+} pmg_mlp_grad;
+int64_t pmg_mlp_grad_work_floats(const pmg_mlp* mlp, int64_t batch);   /* < 0: invalid network / batch */
+int pmg_mlp_grad_device(pmg_env* env, const pmg_mlp* mlp, const pmg_mlp_grad* g);
+
+/* Adam and Polyak: one elementwise launch over the up to eight tensors of a network each.  `shape` supplies the widths and which layers
+ * have a bias; its pointers are not dereferenced.
+ * Adam (normative per element): the host computes in double c1 = 1 - beta1^t, c2 = 1 - beta2^t and passes omb1 = (float)(1 - (double)beta1),
+ * omb2 likewise, step_size = (float)(lr / c1), rsc2 = (float)(1 / sqrt(c2)); on the device
+ *   m = fmaf(beta1, m, omb1 * g);  v = fmaf(beta2, v, omb2 * (g * g));  p = p - step_size * (m / (sqrtf(v) * rsc2 + eps)).
+ * m and v are bit-defined; the step goes through the build's sqrtf and division and is held to a float64 model.
+ * Polyak: t = fmaf(tau, p - t, t), bit-defined (p: the source's parameter, t: the target's).
+ * PMG_E_INVALID: a bad network shape; a NULL or misaligned tensor where the shape has one; lr, eps or a beta not finite; a beta outside
+ * [0, 1); eps < 0; step < 1; tau outside [0, 1] or NaN; a wrong struct_size. */
+typedef struct pmg_adam { int32_t struct_size, reserved; float lr, beta1, beta2, eps; int64_t step; /* t >= 1 */ } pmg_adam;
+int pmg_mlp_adam_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grad,
+                        const pmg_mlp_params* m, const pmg_mlp_params* v, const pmg_adam* a);
+int pmg_mlp_polyak_device(pmg_env* env, const pmg_mlp* source, const pmg_mlp_params* target, float tau);
 
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16

@@ -66,6 +66,23 @@ class PmgTdTarget(C.Structure):
                 ('d_y', C.c_void_p), ('d_q_next', C.c_void_p), ('d_next_action', C.c_void_p)]
 
 
+class PmgMlpParams(C.Structure):
+    _fields_ = [('d_weight', C.c_void_p * 4), ('d_bias', C.c_void_p * 4)]
+
+
+class PmgMlpGrad(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gscale', C.c_float), ('x_dim', C.c_int32), ('a_dim', C.c_int32),
+                ('reserved2', C.c_int32), ('batch', C.c_int64), ('d_x', C.c_void_p), ('x_stride', C.c_int64), ('d_a', C.c_void_p), ('a_stride', C.c_int64),
+                ('d_gout', C.c_void_p), ('gout_stride', C.c_int64), ('d_target', C.c_void_p), ('target_stride', C.c_int64),
+                ('grads', C.POINTER(PmgMlpParams)), ('d_gx', C.c_void_p), ('gx_stride', C.c_int64), ('d_ga', C.c_void_p), ('ga_stride', C.c_int64),
+                ('d_out', C.c_void_p), ('out_stride', C.c_int64), ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
+
+
+class PmgAdam(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
+                ('step', C.c_int64)]
+
+
 class PmgError(RuntimeError):
     pass
 
@@ -85,7 +102,8 @@ class PmgLibrary:
                'pmg_set_sub_goal', 'pmg_curriculum_update', 'pmg_curriculum_read', 'pmg_timing_stats', 'pmg_get_rng', 'pmg_set_rng', 'pmg_comm_timing',
                'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
-               'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device']
+               'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
+               'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -106,6 +124,7 @@ class PmgLibrary:
         for name in self.SYMBOLS:
             if name not in ('pmg_last_error', 'pmg_destroy'):
                 getattr(L, name).restype = C.c_int
+        L.pmg_mlp_grad_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -353,6 +372,44 @@ class PmgHandle:
     def td_target_device(self, actor_target, critic_target, td):
         """y = clip(r + gamma Q'(x', pi'(x'))) of a td_struct(); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_td_target_device(self.h, C.byref(actor_target), C.byref(critic_target), C.byref(td)))
+
+    # -- back-propagation, Adam, Polyak (include/pmg.h, DESIGN.md 3.11) --
+    @staticmethod
+    def params_struct(d_weights, d_biases=None):
+        """pmg_mlp_params from device pointers (integers; a bias may be None)."""
+        p = PmgMlpParams()
+        for l, w in enumerate(d_weights):
+            p.d_weight[l] = w
+            p.d_bias[l] = None if d_biases is None else d_biases[l]
+        return p
+
+    @staticmethod
+    def grad_struct(batch, d_x, x_stride, x_dim, d_work, work_floats, d_a=None, a_stride=0, a_dim=0, d_gout=None, gout_stride=0, d_target=None,
+                    target_stride=0, gscale=1.0, grads=None, d_gx=None, gx_stride=0, d_ga=None, ga_stride=0, d_out=None, out_stride=0):
+        """pmg_mlp_grad from device pointers (integers or None); grads: a params_struct() or None (it must outlive the call)."""
+        return PmgMlpGrad(C.sizeof(PmgMlpGrad), 0, gscale, x_dim, a_dim, 0, batch, d_x, x_stride, d_a, a_stride, d_gout, gout_stride, d_target,
+                          target_stride, C.pointer(grads) if grads is not None else None, d_gx, gx_stride, d_ga, ga_stride, d_out, out_stride,
+                          d_work, work_floats)
+
+    @staticmethod
+    def adam_struct(lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
+        return PmgAdam(C.sizeof(PmgAdam), 0, lr, beta1, beta2, eps, step)
+
+    def mlp_grad_work_floats(self, mlp, batch):
+        """floats of workspace pmg_mlp_grad_device needs for `batch` rows (< 0: invalid network / batch)"""
+        return int(self.L.lib.pmg_mlp_grad_work_floats(C.byref(mlp), C.c_int64(batch)))
+
+    def mlp_grad_device(self, mlp, grad):
+        """forward with saved activations, then backward, of a grad_struct(); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_grad_device(self.h, C.byref(mlp), C.byref(grad)))
+
+    def mlp_adam_device(self, shape, param, grad, m, v, adam):
+        """one Adam step on the tensors of `param` (params_struct()s, adam_struct()); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_adam_device(self.h, C.byref(shape), C.byref(param), C.byref(grad), C.byref(m), C.byref(v), C.byref(adam)))
+
+    def mlp_polyak_device(self, source, target, tau):
+        """target = fmaf(tau, source - target, target) per parameter; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_polyak_device(self.h, C.byref(source), C.byref(target), C.c_float(tau)))
 
     def timing_reset(self):
         self._check(self.L.lib.pmg_timing_reset(self.h))

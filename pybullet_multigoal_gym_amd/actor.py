@@ -13,6 +13,7 @@ stream-ordered calls per step and nothing leaves the GPU:
 import numpy as np
 
 from ._lib import PMG_NORM_OBSERVATION, PMG_NORM_POLICY_STATE
+from .optim import Trainable
 
 KINDS = {'observation': PMG_NORM_OBSERVATION, 'policy_state': PMG_NORM_POLICY_STATE}
 ACTIVATIONS = {'identity': 0, 'tanh': 1}
@@ -52,7 +53,7 @@ def upload_network(h, weights, biases=None, outputs=None):
     return ptrs, [weights[0].shape[1]] + [w.shape[0] for w in weights], d_w, d_b
 
 
-class Actor:
+class Actor(Trainable):
     """``env.actor``: an MLP with ReLU hidden layers on the env's device, and the actions of the env's current rows."""
 
     def __init__(self, env):
@@ -127,7 +128,8 @@ class Actor:
         return out
 
     def close(self):
-        """Free the uploaded network."""
+        """Free the uploaded network and the Adam states made for it."""
+        self._close_states()
         if getattr(self._h, 'h', None):
             for p in self._ptrs:
                 self._h.device_free(p)

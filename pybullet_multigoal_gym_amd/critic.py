@@ -1,21 +1,32 @@
 """The critic of a goal-conditioned DDPG / HER learner on the device: Q(x, a) on two row tables read in place, and the TD target
 y = clip(r + gamma Q'(x', pi'(x'))) of a minibatch in one fused call.
 
-Host-side face of ``pmg_q_device`` and ``pmg_td_target_device`` (include/pmg.h), forward only.  All arithmetic happens
-in the HIP library; this file uploads the network, validates shapes and moves buffers.  The weights live in buffers this object owns
-until ``close()`` (or the next ``load``).  The update side of a device-resident learner starts with two stream-ordered calls:
+Host-side face of ``pmg_q_device`` and ``pmg_td_target_device`` (include/pmg.h); the update side -- gradients, Adam, Polyak
+ -- comes from ``optim.Trainable``, which ``Actor`` shares.  All arithmetic happens in the HIP library; this file uploads
+the network, validates shapes and moves buffers.  The weights live in buffers this object owns until ``close()`` (or the next ``load``).
+There is no learner class: one DDPG / HER update is this sequence of stream-ordered calls, with the online and the target networks in
+four objects (``actor, critic = env.actor, env.critic; actor_t, critic_t = Actor(env), Critic(env)``, all loaded) and nothing leaving the
+GPU:
 
-    env.critic.load(target_critic_weights, target_critic_biases)           # x_dim + a_dim -> ... -> 1
-    env.actor.load(target_actor_weights, target_actor_biases)              # an Actor holds any network: here the target actor
-    h.her_sample_device(rows, E, T, es, ts, B, ..., d_x_next=d_xn, d_reward=d_r, d_goal_achieved=d_ok)
-    env.critic.td_target_device(env.actor, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, d_terminal=d_ok, batch=B)
+    sa, sc = actor.adam_state(), critic.adam_state()                        # once: moments, a gradient buffer .g, t
+    work = max(actor.grad_work_floats(B), critic.grad_work_floats(B)); d_work = h.device_alloc(4 * work)
+    h.her_sample_device(rows, E, T, es, ts, B, ..., d_x=d_x, d_x_next=d_xn, d_action=d_a, d_reward=d_r, d_goal_achieved=d_ok)
+    critic_t.td_target_device(actor_t, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, d_terminal=d_ok, batch=B)          # y
+    critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_a, a_dim=A, d_target=d_y, gscale=2.0 / B, grads=sc.g)          # d mean (Q - y)^2
+    critic.adam_step_device(sc.g, sc, lr)
+    h.mlp_forward_device(actor._loaded(), d_x, Dx, B, d_pi, A)                                                        # a = pi(x)
+    critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_pi, a_dim=A, gscale=-1.0 / B, d_ga=d_ga)                       # d (-mean Q) / da
+    actor.grad_device(B, d_x, Dx, d_work, work, d_gout=d_ga, grads=sa.g)
+    actor.adam_step_device(sa.g, sa, lr)
+    actor_t.soft_update_from(actor, tau); critic_t.soft_update_from(critic, tau)
 """
 import numpy as np
 
 from .actor import ACTIVATIONS, Actor, upload_network
+from .optim import Trainable
 
 
-class Critic:
+class Critic(Trainable):
     """``env.critic``: an MLP with ReLU hidden layers and one output on the env's device."""
 
     def __init__(self, env):
@@ -129,7 +140,8 @@ class Critic:
         return y, qn, na
 
     def close(self):
-        """Free the uploaded network."""
+        """Free the uploaded network and the Adam states made for it."""
+        self._close_states()
         if getattr(self._h, 'h', None):
             for p in self._ptrs:
                 self._h.device_free(p)

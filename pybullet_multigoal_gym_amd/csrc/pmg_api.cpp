@@ -1075,6 +1075,139 @@ int pmg_td_target_device(pmg_env* e, const pmg_mlp* actor_target, const pmg_mlp*
     return PMG_OK;
 }
 
+/* ---- back-propagation, Adam, Polyak ---- */
+int64_t pmg_mlp_grad_work_floats(const pmg_mlp* mlp, int64_t batch)
+{
+    if (!mlp || mlp->struct_size != (int32_t)sizeof(pmg_mlp) || mlp->num_layers < 1 || mlp->num_layers > 4) return -1;
+    if (batch < 0 || batch > ((int64_t)1 << 40)) return -1;
+    PmgMlp M;
+    memset(&M, 0, sizeof(M));
+    M.L = mlp->num_layers;
+    for (int l = 0; l <= M.L; l++) {
+        if (mlp->width[l] < 1 || mlp->width[l] > 256) return -1;
+        M.width[l] = mlp->width[l];
+    }
+    return pmg_grad_work_layout(M, batch, nullptr, nullptr);
+}
+/* the tensors of `p` a network of M's shape has (has_bias[l]: layer l has a bias), all non-null and aligned; extra_bias_ok: a bias pointer
+ * where the network has none is ignored instead of refused; 0 or PMG_E_INVALID */
+static int params_of(pmg_env* e, const PmgMlp& M, const pmg_mlp_params* p, bool extra_bias_ok, const char* who, const char* what)
+{
+    if (!p) return fail(e, PMG_E_INVALID, "%s: %s is null", who, what);
+    for (int l = 0; l < M.L; l++) {
+        if (!p->d_weight[l]) return fail(e, PMG_E_INVALID, "%s: %s d_weight[%d] is null", who, what, l);
+        if (M.b[l] && !p->d_bias[l]) return fail(e, PMG_E_INVALID, "%s: %s d_bias[%d] is null, the network has that bias", who, what, l);
+        if (!M.b[l] && p->d_bias[l] && !extra_bias_ok) return fail(e, PMG_E_INVALID, "%s: %s d_bias[%d] is given, the network has no such bias", who, what, l);
+        if ((((size_t)p->d_weight[l] | (size_t)p->d_bias[l]) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: %s of layer %d are not aligned to 4 bytes", who, what, l);
+    }
+    return PMG_OK;
+}
+
+int pmg_mlp_grad_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_grad_device";
+    PmgMlp M;
+    if (int rc = mlp_of(e, mlp, who, M)) return rc;
+    if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
+    if (g->struct_size != (int32_t)sizeof(pmg_mlp_grad)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_mlp_grad));
+    if (g->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)g->batch);
+    if (!g->d_x || g->x_dim < 1 || g->x_dim > 256) return fail(e, PMG_E_INVALID, "%s: d_x is null or x_dim %d is outside 1..256", who, g->x_dim);
+    if ((g->d_a != nullptr) != (g->a_dim >= 1) || g->a_dim < 0 || g->a_dim > 256)
+        return fail(e, PMG_E_INVALID, "%s: d_a and a_dim %d must be given together (a_dim in 1..256) or be NULL and 0", who, g->a_dim);
+    if (g->x_dim + g->a_dim != M.width[0]) return fail(e, PMG_E_INVALID, "%s: x_dim %d + a_dim %d != width[0] %d", who, g->x_dim, g->a_dim, M.width[0]);
+    if (g->d_ga && !g->d_a) return fail(e, PMG_E_INVALID, "%s: d_ga without d_a", who);
+    if (g->d_gout && g->d_target) return fail(e, PMG_E_INVALID, "%s: both d_gout and d_target are given", who);
+    if (!std::isfinite(g->gscale)) return fail(e, PMG_E_INVALID, "%s: gscale %g is not finite", who, (double)g->gscale);
+    if (!g->grads && !g->d_gx && !g->d_ga && !g->d_out) return fail(e, PMG_E_INVALID, "%s: grads, d_gx, d_ga and d_out are all null: nothing to do", who);
+    if (g->grads) if (int rc = params_of(e, M, g->grads, false, who, "grads")) return rc;
+    const int A = M.width[M.L];
+    if ((((size_t)g->d_x | (size_t)g->d_a | (size_t)g->d_gout | (size_t)g->d_target | (size_t)g->d_gx | (size_t)g->d_ga | (size_t)g->d_out | (size_t)g->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (g->x_stride < g->x_dim || (g->d_a && g->a_stride < g->a_dim) || (g->d_gout && g->gout_stride < A) || (g->d_target && g->target_stride < A) ||
+        (g->d_gx && g->gx_stride < g->x_dim) || (g->d_ga && g->ga_stride < g->a_dim) || (g->d_out && g->out_stride < A))
+        return fail(e, PMG_E_INVALID, "%s: a stride is smaller than its width", who);
+    const int64_t need = pmg_mlp_grad_work_floats(mlp, g->batch);
+    if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)g->batch);
+    if (!g->d_work || g->work_floats < need) return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld < %lld", who, (long long)g->work_floats, (long long)need);
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = g->batch;
+    PmgGrad G;
+    memset(&G, 0, sizeof(G));
+    G.x = g->d_x; G.xs = g->x_stride; G.x_dim = g->x_dim; G.a = g->d_a; G.as = g->a_stride; G.a_dim = g->a_dim;
+    G.gout = g->d_gout; G.gos = g->gout_stride; G.target = g->d_target; G.ts = g->target_stride; G.gscale = g->gscale;
+    G.grads = g->grads ? 1 : 0;
+    for (int l = 0; l < M.L && g->grads; l++) { G.dw[l] = g->grads->d_weight[l]; G.db[l] = M.b[l] ? g->grads->d_bias[l] : nullptr; }
+    G.gx = g->d_gx; G.gxs = g->gx_stride; G.ga = g->d_ga; G.gas = g->ga_stride; G.out = g->d_out; G.os = g->out_stride;
+    pmg_grad_work_layout(M, M.B, g->d_work, &G);
+    HIP_TRY(e, pmg_launch_mlp_grad(M, G, e->stream));
+    return PMG_OK;
+}
+
+/* the segment table of a network's tensors: tensor k of `p` (written) beside tensor k of g / m / v (any may be null for a launcher that
+ * does not use them) */
+static void segs_of(const PmgMlp& M, const pmg_mlp_params* p, const float* const* gw, const float* const* gb, const pmg_mlp_params* m,
+                    const pmg_mlp_params* v, PmgSegs& T)
+{
+    memset(&T, 0, sizeof(T));
+    long long end = 0;
+    for (int l = 0; l < M.L; l++)
+        for (int k = 0; k < 2; k++) {
+            if (k && !M.b[l]) continue;
+            end += k ? M.width[l + 1] : (long long)M.width[l + 1] * M.width[l];
+            const int n = T.n++;
+            T.end[n] = end;
+            T.p[n] = k ? p->d_bias[l] : p->d_weight[l];
+            T.g[n] = k ? gb[l] : gw[l];
+            if (m) T.m[n] = k ? m->d_bias[l] : m->d_weight[l];
+            if (v) T.v[n] = k ? v->d_bias[l] : v->d_weight[l];
+        }
+}
+
+int pmg_mlp_adam_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grad, const pmg_mlp_params* m,
+                        const pmg_mlp_params* v, const pmg_adam* a)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_adam_device";
+    PmgMlp M;
+    if (int rc = mlp_of(e, shape, who, M)) return rc;
+    if (int rc = params_of(e, M, param, true, who, "param")) return rc;
+    if (int rc = params_of(e, M, grad, true, who, "grad")) return rc;
+    if (int rc = params_of(e, M, m, true, who, "m")) return rc;
+    if (int rc = params_of(e, M, v, true, who, "v")) return rc;
+    if (!a) return fail(e, PMG_E_INVALID, "%s: a is null", who);
+    if (a->struct_size != (int32_t)sizeof(pmg_adam)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, a->struct_size, sizeof(pmg_adam));
+    if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !(a->eps >= 0.f)) return fail(e, PMG_E_INVALID, "%s: lr %g must be finite, eps %g finite and >= 0", who, (double)a->lr, (double)a->eps);
+    if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return fail(e, PMG_E_INVALID, "%s: betas %g / %g must lie in [0, 1)", who, (double)a->beta1, (double)a->beta2);
+    if (a->step < 1) return fail(e, PMG_E_INVALID, "%s: step %lld must be >= 1", who, (long long)a->step);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const double c1 = 1.0 - pow((double)a->beta1, (double)a->step), c2 = 1.0 - pow((double)a->beta2, (double)a->step);
+    PmgAdam A;
+    A.beta1 = a->beta1; A.beta2 = a->beta2;
+    A.omb1 = (float)(1.0 - (double)a->beta1); A.omb2 = (float)(1.0 - (double)a->beta2);
+    A.step_size = (float)((double)a->lr / c1); A.rsc2 = (float)(1.0 / sqrt(c2)); A.eps = a->eps;
+    PmgSegs T;
+    segs_of(M, param, grad->d_weight, grad->d_bias, m, v, T);
+    HIP_TRY(e, pmg_launch_adam(T, A, e->stream));
+    return PMG_OK;
+}
+
+int pmg_mlp_polyak_device(pmg_env* e, const pmg_mlp* source, const pmg_mlp_params* target, float tau)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_polyak_device";
+    PmgMlp M;
+    if (int rc = mlp_of(e, source, who, M)) return rc;
+    if (int rc = params_of(e, M, target, true, who, "target")) return rc;
+    if (!(tau >= 0.f && tau <= 1.f)) return fail(e, PMG_E_INVALID, "%s: tau %g is outside [0, 1]", who, (double)tau);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgSegs T;
+    segs_of(M, target, M.w, M.b, nullptr, nullptr, T);
+    HIP_TRY(e, pmg_launch_polyak(T, tau, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

@@ -81,4 +81,32 @@ struct PmgTd {
 };
 hipError_t pmg_launch_mlp_q(const PmgMlp& M, const float* d_x, long long x_stride, int x_dim, const float* d_a, long long a_stride, hipStream_t s);
 hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const PmgTd& T, hipStream_t s);
+
+/* back-propagation, Adam and Polyak (pmg_mlp_grad_device, pmg_mlp_adam_device, pmg_mlp_polyak_device), validated by the caller.
+ * Rows x[r] | a[r] as pmg_launch_mlp_q takes them (a == null: raw rows of x_dim = width[0] floats).  dw / db: the gradient tensors, used iff
+ * grads != 0 (db[l] null where the network has no bias).  wh[l], l >= 1: h_l [B, width[l]]; wd[l]: delta_l [B, width[l + 1]]: the workspace,
+ * cut by pmg_grad_work_layout; both are written and read only when grads != 0. */
+struct PmgGrad {
+    const float* x; long long xs; int x_dim;
+    const float* a; long long as; int a_dim;
+    const float* gout; long long gos;
+    const float* target; long long ts;
+    float gscale;
+    int grads;
+    float* dw[4]; float* db[4];
+    float* gx; long long gxs; float* ga; long long gas; float* out; long long os;
+    float* wh[4]; float* wd[4];
+};
+/* floats of workspace for B rows of network M; with work != null also sets G.wh / G.wd */
+long long pmg_grad_work_layout(const PmgMlp& M, long long B, float* work, PmgGrad* G);
+hipError_t pmg_launch_mlp_grad(const PmgMlp& M, const PmgGrad& G, hipStream_t s);
+/* up to eight tensors swept by one elementwise launch: tensor k owns the flat elements [end[k - 1], end[k]).  Adam: p, g, m, v;
+ * Polyak: p = the target (written), g = the source */
+struct PmgSegs {
+    int n; long long end[8];
+    float* p[8]; const float* g[8]; float* m[8]; float* v[8];
+};
+struct PmgAdam { float beta1, beta2, omb1, omb2, step_size, rsc2, eps; };
+hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
+hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
 #endif

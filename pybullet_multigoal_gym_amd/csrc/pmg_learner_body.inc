@@ -1,7 +1,7 @@
 /* pmg_learner_body.inc -- the learner-side kernels and their launchers (included by pmg_kernels.hip): rewards of [B, G] batches,
- * the running normaliser, policy-input rows, HER minibatches, the actor forward and the critic / TD target (DESIGN.md 3.6-3.10).  None of them
- * touches EnvParams.  What two kernels share has ONE definition, so that they agree bit for bit by construction: reward_of, sq_dist,
- * policy_norm, flat_sweep, mlp_gather, mlp_layers. */
+ * the running normaliser, policy-input rows, HER minibatches, the actor forward, the critic / TD target, and back-propagation, Adam and
+ * Polyak (DESIGN.md 3.6-3.11).  None of them touches EnvParams.  What two kernels share has ONE definition, so that they agree bit for bit
+ * by construction: reward_of, sq_dist, policy_norm, flat_sweep, mlp_gather, mlp_layers, mlp_mma / mlp_chain. */
 /* distance, threshold, binary -> reward value and flag: the one definition (all three reward kernels and pmg_k_her_draw) */
 __device__ __forceinline__ float reward_of(float d, float thr, int binary, unsigned char& ok)
 {
@@ -705,5 +705,354 @@ hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const
 {
     if (actor.B <= 0) return hipSuccess;
     hipLaunchKernelGGL(pmg_k_td_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic, T);
+    return hipGetLastError();
+}
+
+/* Back-propagation through a network (pmg_mlp_grad_device, DESIGN.md 3.11): two kernels.  pmg_k_mlp_grad_rows owns 32 rows per workgroup as
+ * pmg_k_mlp does, on the same tile: gather, the forward layers (mlp_layers_saved: mlp_layers that also keeps every hidden h_l in the
+ * workspace and the sign of every hidden result in registers), the head and delta_{L-1} in place, a thread per (row, unit), then per layer
+ * the TRANSPOSED chain s_l[b][k] = sum over j ascending of delta_l[b][j] W_l[j][k], whose masked result is delta_{l-1}, written to the tile
+ * and to the workspace; s_0 goes to d_gx / d_ga.  pmg_k_mlp_grad_weights then forms dW_l = delta_l^T h_l and db_l from the workspace, one
+ * wavefront per 32 x 32 tile of a dW_l, ONE chain over the batch in ascending row order.
+ * ReLU mask: the backward strip (wave, reg, lane) of layer l is row mlp_row(reg, lane), unit 32 wave (+ 128) + (lane & 31) of h_l -- the very
+ * element the same lane held when the forward wrote h_l.  So the lane keeps `result > 0` of its 2 x 16 results as one 32-bit word per hidden
+ * layer (three words at most) and no h_l is read back: the mask costs no LDS or memory traffic and no barrier.
+ * Stale padding: every write-back covers WHOLE 32-unit strips and puts +0.0 at units past the width, so column `width` of an odd width -- the
+ * A operand of a chain's last step -- holds a real zero under whatever an earlier, wider layer left there; rows past the batch carry
+ * delta = +0.0 from the head on. */
+/* THE transposed matrix step, j0 even: acc[row][unit] = fmaf(tile[row][j0 + 1], W[j0 + 1][unit], fmaf(tile[row][j0], W[j0][unit], acc[row][unit]));
+ * wcol = W + this lane's unit (lane & 31 of the strip), K = floats from row to row of W.  TAIL: the last step of an odd J, j0 = J - 1:
+ * column J of the tile holds zeros and +0.0 stands in for W[J][unit].  Device: A = tile[l & 31][j0 + (l >> 5)] as in mlp_mma,
+ * B = W[j0 + (l >> 5)][unit l & 31]: the lanes run along a row of W (coalesced).  Emulator: fmaf over the lane's own 16 results. */
+template <bool TAIL>
+__device__ __forceinline__ void mlp_mma_t(const float* tile, const float* __restrict__ wcol, int K, int j0, int lane, MlpAcc& acc)
+{
+#ifndef PMG_EMULATE
+    const int h = lane >> 5;
+    const float a = tile[(lane & 31) * MLP_LD + j0 + h];
+    const float b = TAIL ? mlp_keep(wcol[(long long)j0 * K], h == 0) : wcol[(long long)(j0 + h) * K];
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+#else
+    for (int reg = 0; reg < 16; reg++) {
+        const float* a = tile + mlp_row(reg, lane) * MLP_LD + j0;
+        acc[reg] = fmaf(a[1], TAIL ? 0.f : wcol[(long long)(j0 + 1) * K], fmaf(a[0], wcol[(long long)j0 * K], acc[reg]));
+    }
+#endif
+}
+/* all J steps of a transposed layer for the NS = 1 or 2 strips of a wavefront (mlp_chain's shape: eight steps written out) */
+template <int NS>
+__device__ __forceinline__ void mlp_chain_t(const float* tile, const float* __restrict__ w0, const float* __restrict__ w1, int J, int K, int lane,
+                                            MlpAcc& acc0, MlpAcc& acc1)
+{
+    const int J16 = J & ~15, Je = J & ~1;
+    for (int j0 = 0; j0 < J16; j0 += 16) {
+#pragma unroll
+        for (int u = 0; u < 16; u += 2) {
+            mlp_mma_t<false>(tile, w0, K, j0 + u, lane, acc0);
+            if (NS == 2) mlp_mma_t<false>(tile, w1, K, j0 + u, lane, acc1);
+        }
+    }
+    for (int j0 = J16; j0 < Je; j0 += 2) {
+        mlp_mma_t<false>(tile, w0, K, j0, lane, acc0);
+        if (NS == 2) mlp_mma_t<false>(tile, w1, K, j0, lane, acc1);
+    }
+    if (J & 1) {
+        mlp_mma_t<true>(tile, w0, K, Je, lane, acc0);
+        if (NS == 2) mlp_mma_t<true>(tile, w1, K, Je, lane, acc1);
+    }
+}
+/* mlp_layers for the gradient: the same chains on the same tile, and per hidden layer l -> h_{l + 1}: the lane's 2 x 16 signs into
+ * m1 / m2 / m3 (bit reg: strip `wave`, bit 16 + reg: strip `wave + 4`; a result that is exactly 0 or a NaN has mask 0) and, when the
+ * weights kernel will run, h_{l + 1} of the rows of the batch into the workspace (lanes along the units: coalesced) */
+__device__ __forceinline__ void mlp_layers_saved(float* tile, const PmgMlp& M, const PmgGrad& G, long long row0, int lane, int wave, int col,
+                                                 unsigned int& m1, unsigned int& m2, unsigned int& m3)
+{
+#pragma unroll 1
+    for (int l = 0; l < M.L; l++) {
+        const int K = M.width[l], Nn = M.width[l + 1];
+        const float* __restrict__ W = M.w[l];
+        const float* __restrict__ bias = M.b[l];
+        const int u0 = 32 * wave + col, u1 = u0 + 128;
+        const bool live0 = u0 < Nn, live1 = u1 < Nn, strip0 = 32 * wave < Nn, strip1 = 32 * wave + 128 < Nn;
+        const float* w0 = W + (long long)(live0 ? u0 : 0) * K;
+        const float* w1 = W + (long long)(live1 ? u1 : 0) * K;
+        const float b0 = bias ? bias[live0 ? u0 : 0] : 0.f, b1 = bias ? bias[live1 ? u1 : 0] : 0.f;
+        MlpAcc acc0, acc1;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { acc0[reg] = b0; acc1[reg] = b1; }
+        if (strip1) mlp_chain<2>(tile, w0, w1, K, lane, acc0, acc1);
+        else if (strip0) mlp_chain<1>(tile, w0, w1, K, lane, acc0, acc1);
+        const bool hidden = l + 1 < M.L;
+        float* __restrict__ H = hidden && G.grads ? G.wh[l + 1] : nullptr;
+        unsigned int mask = 0;
+        __syncthreads();                                         /* every wavefront has read the layer's input */
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int r = mlp_row(reg, lane);
+            const bool inb = row0 + r < M.B;
+            if (strip0) {
+                const float v = live0 ? (hidden ? fmaxf(acc0[reg], 0.f) : acc0[reg]) : 0.f;
+                tile[r * MLP_LD + u0] = v;
+                mask |= (unsigned int)(live0 && acc0[reg] > 0.f) << reg;
+                if (H && live0 && inb) H[(row0 + r) * Nn + u0] = v;
+            }
+            if (strip1) {
+                const float v = live1 ? (hidden ? fmaxf(acc1[reg], 0.f) : acc1[reg]) : 0.f;
+                tile[r * MLP_LD + u1] = v;
+                mask |= (unsigned int)(live1 && acc1[reg] > 0.f) << (16 + reg);
+                if (H && live1 && inb) H[(row0 + r) * Nn + u1] = v;
+            }
+        }
+        if (l == 0) m1 = mask; else if (l == 1) m2 = mask; else if (l == 2) m3 = mask;
+        __syncthreads();
+    }
+}
+/* s_0[row][c] to where it belongs: column c < x_dim of d_gx, the others of d_ga (either may be null) */
+__device__ __forceinline__ void grad_input_store(const PmgGrad& G, long long row, int c, float v)
+{
+    if (c < G.x_dim) { if (G.gx) G.gx[row * G.gxs + c] = v; }
+    else if (G.ga) G.ga[row * G.gas + (c - G.x_dim)] = v;
+}
+/* the transposed layers on a tile whose columns [0, width[L] rounded up to even) hold delta_{L-1} (rows past the batch and the padding
+ * column: +0.0); layer 0 runs only when an input gradient is wanted */
+__device__ __forceinline__ void mlp_backward(float* tile, const PmgMlp& M, const PmgGrad& G, long long row0, int lane, int wave, int col,
+                                             unsigned int m1, unsigned int m2, unsigned int m3)
+{
+#pragma unroll 1
+    for (int l = M.L - 1; l >= 0; l--) {
+        if (l == 0 && !G.gx && !G.ga) break;
+        const int J = M.width[l + 1], K = M.width[l];
+        const float* __restrict__ W = M.w[l];
+        const int k0 = 32 * wave + col, k1 = k0 + 128;            /* this lane's input unit in the strips wave and wave + 4 */
+        const bool live0 = k0 < K, live1 = k1 < K, strip0 = 32 * wave < K, strip1 = 32 * wave + 128 < K;
+        /* a unit past the width runs on column 0 of W: valid addresses, results never used */
+        const float* w0 = W + (live0 ? k0 : 0);
+        const float* w1 = W + (live1 ? k1 : 0);
+        MlpAcc acc0, acc1;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { acc0[reg] = 0.f; acc1[reg] = 0.f; }
+        if (strip1) mlp_chain_t<2>(tile, w0, w1, J, K, lane, acc0, acc1);
+        else if (strip0) mlp_chain_t<1>(tile, w0, w1, J, K, lane, acc0, acc1);
+        __syncthreads();                                         /* every wavefront has read delta_l */
+        if (l > 0) {
+            const unsigned int mask = l == 1 ? m1 : (l == 2 ? m2 : m3);
+            float* __restrict__ D = G.grads ? G.wd[l - 1] : nullptr;
+            /* whole strips: a masked unit and a unit past the width become a real +0.0 */
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const int r = mlp_row(reg, lane);
+                const bool inb = row0 + r < M.B;
+                if (strip0) {
+                    const float v = live0 && ((mask >> reg) & 1u) ? acc0[reg] : 0.f;
+                    tile[r * MLP_LD + k0] = v;
+                    if (D && live0 && inb) D[(row0 + r) * K + k0] = v;
+                }
+                if (strip1) {
+                    const float v = live1 && ((mask >> (16 + reg)) & 1u) ? acc1[reg] : 0.f;
+                    tile[r * MLP_LD + k1] = v;
+                    if (D && live1 && inb) D[(row0 + r) * K + k1] = v;
+                }
+            }
+            __syncthreads();
+        } else {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) {
+                const long long row = row0 + mlp_row(reg, lane);
+                if (row >= M.B) continue;
+                if (live0) grad_input_store(G, row, k0, acc0[reg]);
+                if (live1) grad_input_store(G, row, k1, acc1[reg]);
+            }
+        }
+    }
+}
+template <class Src>
+__global__ void __launch_bounds__(256, 2) pmg_k_mlp_grad_rows(Src S, PmgMlp M, PmgGrad G)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int A = M.width[M.L];
+    const long long ntiles = (M.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, M.B, M.width[0], (M.width[0] + 1) & ~1, t);
+        __syncthreads();
+        unsigned int m1 = 0, m2 = 0, m3 = 0;
+        mlp_layers_saved(tile, M, G, row0, lane, wave, col, m1, m2, m3);
+        /* the tile holds z (and +0.0 up to the end of z's last strip): head and delta_{L-1} in place, thread per (row, unit) */
+        for (int i = t; i < MLP_ROWS * A; i += 256) {
+            const int r = i / A, j = i - r * A;
+            const long long row = row0 + r;
+            float d = 0.f;
+            if (row < M.B) {
+                const float z = tile[r * MLP_LD + j], o = M.out_act ? tanhf(z) : z;
+                if (G.out) G.out[row * G.os + j] = o;
+                float g = G.gscale;
+                if (G.gout) g = G.gout[row * G.gos + j];
+                else if (G.target) { const float e = o - G.target[row * G.ts + j]; g = G.gscale * e; }
+                d = M.out_act ? g * fmaf(-o, o, 1.f) : g;
+                if (G.grads) G.wd[M.L - 1][row * A + j] = d;
+            }
+            tile[r * MLP_LD + j] = d;
+        }
+        __syncthreads();
+        mlp_backward(tile, M, G, row0, lane, wave, col, m1, m2, m3);   /* ends behind a barrier: the next tile's rows may overwrite this one's */
+    }
+}
+/* column col of the rows of a source as a pointer and the floats from row to row.  A lane of the weights kernel keeps ITS column for the
+ * whole chain, so which table the column lives in is decided once, outside the loop, and the loop holds plain loads (MlpCatRows::at inside
+ * it would be a select fed by two loads) */
+__device__ __forceinline__ const float* mlp_column(const MlpRawRows& S, int col, long long& stride) { stride = S.stride; return S.in + col; }
+__device__ __forceinline__ const float* mlp_column(const MlpCatRows& S, int col, long long& stride)
+{
+    const bool in_x = col < S.Dx;
+    stride = in_x ? S.xs : S.as;
+    return in_x ? S.x + col : S.a + (col - S.Dx);
+}
+/* h_l[b][this lane's unit]: the workspace (l >= 1) or the row source (l == 0) */
+struct GradHCol { const float* __restrict__ p; long long stride; __device__ __forceinline__ float operator()(long long b) const { return p[b * stride]; } };
+/* one step of a dW tile, b0 even: acc[j][k] = fmaf(delta[b0 + 1][j], h[b0 + 1][k], fmaf(delta[b0][j], h[b0][k], acc[j][k])) for the 32 units
+ * j from jb and the lane's input unit kl (clamped, as jb's units are); BIAS: accb[j][*] likewise with 1 in place of h -- fmaf(delta, 1, acc)
+ * is acc + delta exactly.  TAIL: the last step of an odd batch, b0 = B - 1: row B is +0.0 on both sides, from the valid row B - 1 through
+ * mlp_keep.  Device: A = delta[b0 + (l >> 5)][jb + (l & 31)], B = h[b0 + (l >> 5)][the lane's unit]: both run along a row (coalesced).  hf(b) = h_l[b][that unit]. */
+template <bool TAIL, bool BIAS>
+__device__ __forceinline__ void grad_w_mma(const float* __restrict__ delta, int J, int jb, const GradHCol& hf, long long b0, int lane,
+                                           MlpAcc& acc, MlpAcc& accb)
+{
+#ifndef PMG_EMULATE
+    const int h = lane >> 5, j = jb + (lane & 31);
+    const bool in = !TAIL || h == 0;
+    const long long b = in ? b0 + h : b0;
+    float a = delta[b * J + (j < J ? j : 0)], v = hf(b);
+    if (TAIL) { a = mlp_keep(a, in); v = mlp_keep(v, in); }
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, v, acc, 0, 0, 0);
+    if (BIAS) accb = __builtin_amdgcn_mfma_f32_32x32x2f32(a, 1.f, accb, 0, 0, 0);
+#else
+    const float h0 = hf(b0), h1 = TAIL ? 0.f : hf(b0 + 1);
+    for (int reg = 0; reg < 16; reg++) {
+        const int j = jb + mlp_row(reg, lane), jl = j < J ? j : 0;
+        const float a0 = delta[b0 * J + jl], a1 = TAIL ? 0.f : delta[(b0 + 1) * J + jl];
+        acc[reg] = fmaf(a1, h1, fmaf(a0, h0, acc[reg]));
+        if (BIAS) accb[reg] = fmaf(a1, 1.f, fmaf(a0, 1.f, accb[reg]));
+    }
+#endif
+}
+/* the whole chain over the batch of one dW tile, rows ascending, and its stores.  Eight steps are written out, as in mlp_chain */
+template <bool BIAS>
+__device__ __forceinline__ void grad_w_tile(const float* __restrict__ delta, int J, int K, int jb, int k, const GradHCol& hf, long long B, int lane,
+                                            float* __restrict__ dw, float* __restrict__ db)
+{
+    MlpAcc acc, accb;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) { acc[reg] = 0.f; accb[reg] = 0.f; }
+    const long long B16 = B & ~15ll, Be = B & ~1ll;
+    for (long long b0 = 0; b0 < B16; b0 += 16) {
+#pragma unroll
+        for (int u = 0; u < 16; u += 2) grad_w_mma<false, BIAS>(delta, J, jb, hf, b0 + u, lane, acc, accb);
+    }
+    for (long long b0 = B16; b0 < Be; b0 += 2) grad_w_mma<false, BIAS>(delta, J, jb, hf, b0, lane, acc, accb);
+    if (B & 1) grad_w_mma<true, BIAS>(delta, J, jb, hf, Be, lane, acc, accb);
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+        const int j = jb + mlp_row(reg, lane);
+        if (j >= J) continue;
+        if (k < K) dw[(long long)j * K + k] = acc[reg];
+        if (BIAS && (lane & 31) == 0) db[j] = accb[reg];
+    }
+}
+/* one wavefront per 32 x 32 tile of a dW_l, the tiles of layer 0 first; the tiles of input strip 0 carry the bias sums of their units */
+template <class Src>
+__global__ void __launch_bounds__(64) pmg_k_mlp_grad_weights(Src S, PmgMlp M, PmgGrad G)
+{
+    int tile = (int)blockIdx.x, l = 0, tk = 0;
+    for (;; l++) {
+        tk = (M.width[l] + 31) / 32;
+        const int n = ((M.width[l + 1] + 31) / 32) * tk;
+        if (tile < n || l + 1 == M.L) break;
+        tile -= n;
+    }
+    const int J = M.width[l + 1], K = M.width[l], jb = 32 * (tile / tk), kb = 32 * (tile % tk), lane = (int)threadIdx.x;
+    const int k = kb + (lane & 31), kl = k < K ? k : 0;           /* a unit past the width runs on column 0: valid addresses, never stored */
+    GradHCol hf;
+    if (l == 0) hf.p = mlp_column(S, kl, hf.stride);
+    else { hf.p = G.wh[l] + kl; hf.stride = K; }
+    if (kb == 0 && G.db[l] != nullptr) grad_w_tile<true>(G.wd[l], J, K, jb, k, hf, M.B, lane, G.dw[l], G.db[l]);
+    else grad_w_tile<false>(G.wd[l], J, K, jb, k, hf, M.B, lane, G.dw[l], G.db[l]);
+}
+long long pmg_grad_work_layout(const PmgMlp& M, long long B, float* work, PmgGrad* G)
+{
+    long long per_row = 0;
+    for (int l = 1; l < M.L; l++) {
+        if (work) G->wh[l] = work + per_row * B;
+        per_row += M.width[l];
+    }
+    for (int l = 0; l < M.L; l++) {
+        if (work) G->wd[l] = work + per_row * B;
+        per_row += M.width[l + 1];
+    }
+    return per_row * B;
+}
+template <class Src>
+static void launch_mlp_grad(const Src& S, const PmgMlp& M, const PmgGrad& G, hipStream_t s)
+{
+    hipLaunchKernelGGL((pmg_k_mlp_grad_rows<Src>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M, G);
+    if (!G.grads) return;
+    int tiles = 0;
+    for (int l = 0; l < M.L; l++) tiles += ((M.width[l + 1] + 31) / 32) * ((M.width[l] + 31) / 32);
+    hipLaunchKernelGGL((pmg_k_mlp_grad_weights<Src>), dim3(tiles), dim3(64), 0, s, S, M, G);
+}
+hipError_t pmg_launch_mlp_grad(const PmgMlp& M, const PmgGrad& G, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    if (G.a) launch_mlp_grad(MlpCatRows{G.x, G.xs, G.a, G.as, G.x_dim}, M, G, s);
+    else launch_mlp_grad(MlpRawRows{G.x, G.xs}, M, G, s);
+    return hipGetLastError();
+}
+
+/* Adam and Polyak (pmg_mlp_adam_device, pmg_mlp_polyak_device, DESIGN.md 3.11): one elementwise sweep over the up to eight tensors of a
+ * network.  HBM-bound; a thread finds the tensor of its flat element by comparing against the table's prefix ends (statically indexed:
+ * the table stays in scalar registers).  Dword accesses: the tensors come with any 4-byte alignment. */
+struct SegAt { float* p; const float* g; float* m; float* v; long long i; };
+__device__ __forceinline__ SegAt seg_at(const PmgSegs& T, long long i)
+{
+    SegAt a = {T.p[0], T.g[0], T.m[0], T.v[0], i};
+#pragma unroll
+    for (int k = 1; k < 8; k++)
+        if (k < T.n && i >= T.end[k - 1]) { a.p = T.p[k]; a.g = T.g[k]; a.m = T.m[k]; a.v = T.v[k]; a.i = i - T.end[k - 1]; }
+    return a;
+}
+__global__ void __launch_bounds__(256) pmg_k_adam(PmgSegs T, PmgAdam A)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const SegAt s = seg_at(T, i);
+        const float g = s.g[s.i];
+        const float m = fmaf(A.beta1, s.m[s.i], A.omb1 * g);
+        const float v = fmaf(A.beta2, s.v[s.i], A.omb2 * (g * g));
+        s.m[s.i] = m; s.v[s.i] = v;
+        s.p[s.i] = s.p[s.i] - A.step_size * (m / (sqrtf(v) * A.rsc2 + A.eps));
+    }
+}
+__global__ void __launch_bounds__(256) pmg_k_polyak(PmgSegs T, float tau)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const SegAt s = seg_at(T, i);
+        const float t = s.p[s.i];
+        s.p[s.i] = fmaf(tau, s.g[s.i] - t, t);
+    }
+}
+static unsigned seg_grid(const PmgSegs& T)
+{
+    const long long want = (T.end[T.n - 1] + 255) / 256;
+    return (unsigned)(want < 2048 ? want : 2048);
+}
+hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_adam, dim3(seg_grid(T)), dim3(256), 0, s, T, A);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_polyak, dim3(seg_grid(T)), dim3(256), 0, s, T, tau);
     return hipGetLastError();
 }
