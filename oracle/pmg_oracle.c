@@ -57,7 +57,7 @@ typedef double real;
 /* ------------------------------------------------------------------ */
 enum { PRIOR_MOTOR_IMPULSE_DT, PRIOR_LINK_DAMPING, PRIOR_JOINT_ERP, PRIOR_CONTACT_MARGIN, PRIOR_RESIDUAL_THRESHOLD,
        PRIOR_IK_DAMPING, PRIOR_LINEAR_SLOP, PRIOR_WARM_START, PRIOR_DAMPING_PER_SUBSTEP, PRIOR_FRICTION_DIRS,
-       PRIOR_SOLVER_ITERATIONS, PRIOR_CONTACT_WARM_START, PRIOR_STATE_F32, PRIOR_N };
+       PRIOR_SOLVER_ITERATIONS, PRIOR_CONTACT_WARM_START, PRIOR_STATE_F32, PRIOR_SIM_STEPS, PRIOR_SUBSTEPS, PRIOR_N };
 static const char* const PRIOR_NAME[PRIOR_N] = {
     "motor_impulse_dt",     /* 0.04: max motor impulse = force x fixedTimeStep; 0.002 = force x substep */
     "link_damping",         /* 0.04: btMultiBody linear / angular damping; 0 = none */
@@ -78,14 +78,18 @@ static const char* const PRIOR_NAME[PRIOR_N] = {
                              * f in (0, 1]: Bullet's persistent-manifold behaviour for rigid bodies -- a contact point that
                              * persists (same pair, within the 0.02 breaking threshold of a cached point) starts from
                              * f x its last normal impulse (btSequentialImpulseConstraintSolver: f = 0.85) */
-    "state_f32_per_substep" /* 0.  NOT a prior, a yardstick: 1 = joint / block / door positions and velocities are rounded to
+    "state_f32_per_substep",/* 0.  NOT a prior, a yardstick: 1 = joint / block / door positions and velocities are rounded to
                              * float32 at the end of every substep while all arithmetic stays float64 -- the best any
                              * implementation that KEEPS ITS STATE in float32 can do.  Its deviation from the plain float64
                              * oracle is the chaos floor of tools/teacher_forced.py (how often a single env step bifurcates
                              * under float32-sized state noise, whatever the arithmetic) */
+    "sim_steps",            /* 5.  NOT a prior (kuka.py:223-225 sets it): how many stepSimulation() calls env_step_one RUNS */
+    "substeps"              /* 20.  NOT a prior (base_env.py:219): how many substeps one stepSimulation() RUNS.  Both bound
+                             * loops only (SUBSTEP_DT, the motor impulses and `elapsed` stay); 1 / 1 = one substep() per env
+                             * step, the reference of the product's one-substep test builds (tests/test_substep_emulated.py) */
 };
-static double G_PRIOR[PRIOR_N] = {0.04, 0.04, 0.2, 0.002, 1e-7, 0.5, 1e-5, 0.0, 0.0, 2.0, 5.0, 0.0, 0.0};
-static const double PRIOR_DEFAULT[PRIOR_N] = {0.04, 0.04, 0.2, 0.002, 1e-7, 0.5, 1e-5, 0.0, 0.0, 2.0, 5.0, 0.0, 0.0};
+static double G_PRIOR[PRIOR_N] = {0.04, 0.04, 0.2, 0.002, 1e-7, 0.5, 1e-5, 0.0, 0.0, 2.0, 5.0, 0.0, 0.0, 5.0, 20.0};
+static const double PRIOR_DEFAULT[PRIOR_N] = {0.04, 0.04, 0.2, 0.002, 1e-7, 0.5, 1e-5, 0.0, 0.0, 2.0, 5.0, 0.0, 0.0, 5.0, 20.0};
 
 /* ------------------------------------------------------------------ */
 /* constants                                    */
@@ -118,6 +122,7 @@ static const double PRIOR_DEFAULT[PRIOR_N] = {0.04, 0.04, 0.2, 0.002, 1e-7, 0.5,
 #define GBASE_FRICTION ((real)0.5)     /* [BULLET-PRIOR] btCollisionObject default friction (no <contact> tag) */
 #define EDGE_FUDGE ((real)1.05)        /* [BULLET-PRIOR] btBoxBoxDetector fudge_factor */
 #define MAX_CONTACTS 64
+_Static_assert(MAX_CONTACTS == PMGO_MAX_CONTACTS, "pmgo_last_substep's array length");
 #define PI_R ((real)3.14159265358979323846)
 
 static const int JPARENT_BL[NL] = PMG_BL_PARENT;
@@ -1483,7 +1488,9 @@ typedef struct {
     real ws_m[NJ], ws_l[NJ]; /* last substep's motor / limit impulses (only read with the warm_start prior) */
     int wsc_n;               /* last substep's contacts: pair, point on A, normal impulse (contact_warm_start prior only) */
     int wsc_a[MAX_CONTACTS], wsc_b[MAX_CONTACTS];
-    real wsc_p[MAX_CONTACTS][3], wsc_imp[MAX_CONTACTS];
+    real wsc_p[MAX_CONTACTS][3], wsc_imp[MAX_CONTACTS], wsc_dist[MAX_CONTACTS];
+    int wsc_iters;           /* solver iterations the last substep ran, and the residual of each (pmgo_last_substep) */
+    real wsc_resid[PMGO_MAX_SOLVER_ITERS];
     mt19937 rng;
 } World;
 
@@ -1951,6 +1958,7 @@ static void substep(const pmgo_env* e, World* w, const real* tau)
                 if (r->blk[s2] >= 0) { v3axpy(dbl[r->blk[s2]], a0, r->dl[s2]); v3axpy(dba[r->blk[s2]], a0, r->da[s2]); }
         }
     const int solver_iters = (int)G_PRIOR[PRIOR_SOLVER_ITERATIONS];
+    w->wsc_iters = 0;
     for (int it = 0; it < solver_iters; it++) {
         real resid = 0;
         for (int j = 0; j < nn; j++) {
@@ -1976,12 +1984,14 @@ static void substep(const pmgo_env* e, World* w, const real* tau)
                 resid = dv * dv > resid ? dv * dv : resid;
             }
         }
+        if (it < PMGO_MAX_SOLVER_ITERS) w->wsc_resid[it] = resid;
+        w->wsc_iters = it + 1;
         if (resid <= RESIDUAL_THRESHOLD) break;
     }
     w->wsc_n = nc;
     for (int c = 0; c < nc; c++) {
         w->wsc_a[c] = con[c].a; w->wsc_b[c] = con[c].b; w->wsc_imp[c] = nrm[c].applied;
-        v3cpy(w->wsc_p[c], con[c].pa);
+        v3cpy(w->wsc_p[c], con[c].pa); w->wsc_dist[c] = con[c].dist;
     }
     for (int d = 0; d < NJ; d++) { w->ws_m[d] = 0; w->ws_l[d] = 0; }
     for (int j = 0; j < nn; j++) {
@@ -2029,7 +2039,8 @@ static void step_simulation(const pmgo_env* e, World* w)
 {
     real tau[NJ];
     for (int d = 0; d < NJ; d++) tau[d] = -(real)JDAMP[d] * w->qd[d];
-    for (int s = 0; s < SUBSTEPS; s++) {
+    const int substeps = (int)G_PRIOR[PRIOR_SUBSTEPS];
+    for (int s = 0; s < substeps; s++) {
         if (G_PRIOR[PRIOR_DAMPING_PER_SUBSTEP] != 0)
             for (int d = 0; d < NJ; d++) tau[d] = -(real)JDAMP[d] * w->qd[d];
         substep(e, w, tau);
@@ -2116,7 +2127,7 @@ static void tip_state(const World* w, const Kin* k, real* pos, real* vel, real* 
 static void robot_reset(const pmgo_env* e, World* w)
 {
     real tq[4] = {(real)TOOL_QUAT[0], (real)TOOL_QUAT[1], (real)TOOL_QUAT[2], (real)TOOL_QUAT[3]};
-    w->wsc_n = 0;
+    w->wsc_n = 0; w->wsc_iters = 0;
     for (int d = 0; d < 7; d++) { w->q[d] = w->rest_pose[d]; w->qd[d] = 0; w->motor_maximp[d] = 0; } /* :158 + robot_bases.py:230-238 */
     real qo[NJ];
     ik_solve(w->q, e->tip_init, tq, IK_MAX_ITER, IK_THRESHOLD, qo);                                    /* :159 */
@@ -2526,7 +2537,8 @@ static void env_step_one(const pmgo_env* e, World* w, const float* a)
     }
     for (int d = 0; d < 7; d++) { w->motor_target[d] = poses[d]; w->motor_maximp[d] = ARM_FORCE * PHYSICS_DT; } /* :222, :282-290 */
     w->arm_enabled = 1;
-    for (int s = 0; s < SIM_STEPS; s++) step_simulation(e, w);                         /* :223-225 */
+    const int sim_steps = (int)G_PRIOR[PRIOR_SIM_STEPS];
+    for (int s = 0; s < sim_steps; s++) step_simulation(e, w);                         /* :223-225 */
     /* _get_obs keeps a door it finds open open: from now on the position motor holds it (:296-298) */
     if (e->chest >= 0 && RFABS(e->door_open - DOOR_Q(w)) <= (real)0.01) DOOR_MOTOR(w) = 1;
     w->elapsed++;
@@ -2751,7 +2763,7 @@ int pmgo_set_state(pmgo_env* e, const float* state)
         World* w = &e->w[i];
         const float* s = state + (size_t)i * S;
         for (int d = 0; d < 9; d++) { w->q[d] = s[d]; w->qd[d] = s[9 + d]; }
-        w->wsc_n = 0;
+        w->wsc_n = 0; w->wsc_iters = 0;
         for (int a = 0; a < 3; a++) w->ee_target[a] = s[18 + a];
         for (int d = 0; d < 7; d++) { w->joint_target[d] = s[21 + d]; w->rest_pose[d] = s[32 + d]; }
         w->grip_target = s[28]; w->elapsed = (int)s[29]; w->arm_enabled = (int)s[30]; w->reset_count = (int)s[31];
@@ -2905,6 +2917,25 @@ int pmgo_bw_ik(pmgo_env* e, const double pos[3], const double quat[4], int max_i
 int pmgo_bw_step_simulation(pmgo_env* e)
 {
     step_simulation(e, bw_world(e));
+    return PMG_OK;
+}
+
+/* read-out of env i's last substep: the contacts in solve order and the solver's course */
+int pmgo_last_substep(const pmgo_env* e, int i, int32_t* n_contacts, int32_t* a, int32_t* b, double* point_a, double* distance,
+                      double* impulse, int32_t* iterations, double* residual)
+{
+    if (!e || i < 0 || i >= e->cfg.num_envs) return PMG_E_INVALID;
+    const World* w = &e->w[i];
+    if (n_contacts) *n_contacts = w->wsc_n;
+    for (int c = 0; c < w->wsc_n; c++) {
+        if (a) a[c] = w->wsc_a[c];
+        if (b) b[c] = w->wsc_b[c];
+        if (point_a) for (int k = 0; k < 3; k++) point_a[3 * c + k] = (double)w->wsc_p[c][k];
+        if (distance) distance[c] = (double)w->wsc_dist[c];
+        if (impulse) impulse[c] = (double)w->wsc_imp[c];
+    }
+    if (iterations) *iterations = w->wsc_iters;
+    if (residual) for (int k = 0; k < PMGO_MAX_SOLVER_ITERS; k++) residual[k] = k < w->wsc_iters ? (double)w->wsc_resid[k] : 0.0;
     return PMG_OK;
 }
 

@@ -47,6 +47,15 @@ int pmgo_curriculum_update(pmgo_env* env, int32_t enabled);
 int pmgo_curriculum_read(pmgo_env* env, int32_t* level, int32_t* goal_step, float* prob, float* generated);
 int pmgo_set_threads(pmgo_env* env, int nthreads);   /* OpenMP threads for the env loop */
 
+/* Read-out of env i's LAST substep (whatever step ran it): the contact count, per contact in solve order the body ids a, b,
+ * the point on A (point_a[3 * c ..]), the narrowphase distance (negative: penetration) and the final normal impulse, then the number of solver iterations run and the residual
+ * (largest squared velocity change of a row) of each of them.  Arrays: PMGO_MAX_CONTACTS entries (3 x for point_a),
+ * residual PMGO_MAX_SOLVER_ITERS; any pointer may be NULL. */
+#define PMGO_MAX_CONTACTS 64
+#define PMGO_MAX_SOLVER_ITERS 8
+int pmgo_last_substep(const pmgo_env* env, int i, int32_t* n_contacts, int32_t* a, int32_t* b, double* point_a,
+                      double* distance, double* impulse, int32_t* iterations, double* residual);
+
 /* ---- probes used by the unit tests (double precision, single env) ---- */
 /* forward kinematics of the 9-dof chain: tip position, rotation (row-major 3x3) */
 void pmgo_fk_tip(const double q[9], double pos[3], double rot[9]);

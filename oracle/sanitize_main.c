@@ -1,6 +1,6 @@
 /* TEST INFRASTRUCTURE: driver of the AddressSanitizer / UndefinedBehaviorSanitizer build of the oracle
  * (tests/test_sanitizers.py).  Every task, with its options, through create / reset / masked
- * reset / random steps / compute_reward / get_state / set_state / destroy. */
+ * reset / random steps / compute_reward / get_state / set_state / a one-substep step + pmgo_last_substep / destroy. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -50,6 +50,20 @@ int main(void)
             pmgo_get_state(e, st);
             pmgo_set_state(e, st);
             rc_all |= pmgo_step(e, act, obs, pol, ag, dg, r, ok, dn);
+            /* one substep per env step (the sim_steps / substeps switches), then the read-out of every env's last substep */
+            rc_all |= pmgo_set_prior("sim_steps", 1.0) | pmgo_set_prior("substeps", 1.0);
+            rc_all |= pmgo_step(e, act, obs, pol, ag, dg, r, ok, dn);
+            pmgo_reset_priors();
+            for (int i = 0; i < N; i++) {
+                int32_t nc = -1, ca[PMGO_MAX_CONTACTS], cb[PMGO_MAX_CONTACTS], iters = -1;
+                double pa[3 * PMGO_MAX_CONTACTS], dist[PMGO_MAX_CONTACTS], imp[PMGO_MAX_CONTACTS], resid[PMGO_MAX_SOLVER_ITERS];
+                rc_all |= pmgo_last_substep(e, i, &nc, ca, cb, pa, dist, imp, &iters, resid);
+                double sum = 0;
+                for (int k = 0; k < nc; k++) sum += pa[3 * k] + pa[3 * k + 1] + pa[3 * k + 2] + dist[k] + imp[k] + ca[k] + cb[k];
+                for (int k = 0; k < PMGO_MAX_SOLVER_ITERS; k++) sum += resid[k];
+                if (nc < 0 || nc > PMGO_MAX_CONTACTS || iters < 1 || iters > 5 || sum != sum) rc_all |= 1;
+            }
+            rc_all |= pmgo_last_substep(e, N, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == 0;   /* out of range: refused */
             free(obs); free(pol); free(ag); free(dg); free(act); free(st);
             pmgo_destroy(e);
         }

@@ -23,6 +23,18 @@ constexpr int NJ = 9;
 constexpr float DT = 0.002f;            /* base_env.py:217-219 */
 constexpr int SUBSTEPS = 20;            /* base_env.py:219 */
 constexpr int SIM_STEPS = 5;            /* kuka.py:223-225 */
+/* How many of them a kernel RUNS per env step.  The product runs all of them; a test build (-DPMG_RUN_SIM_STEPS=1
+ * -DPMG_RUN_SUBSTEPS=1) stops after the first, so that one substep() can be held to the float64 oracle before contact chaos
+ * sets in (tests/test_substep_emulated.py).  Only the loop bounds read these: DT, PHYSICS_DT, the motor impulses and
+ * `elapsed` do not depend on them. */
+#ifndef PMG_RUN_SIM_STEPS
+#define PMG_RUN_SIM_STEPS SIM_STEPS
+#endif
+#ifndef PMG_RUN_SUBSTEPS
+#define PMG_RUN_SUBSTEPS SUBSTEPS
+#endif
+constexpr int RUN_SIM_STEPS = PMG_RUN_SIM_STEPS;
+constexpr int RUN_SUBSTEPS = PMG_RUN_SUBSTEPS;
 constexpr int SOLVER_ITERS = 5;         /* base_env.py:37 */
 constexpr float PHYSICS_DT = 0.04f;     /* base_env.py:217 */
 constexpr float GRAVITY = 9.81f;        /* base_env.py:17 */

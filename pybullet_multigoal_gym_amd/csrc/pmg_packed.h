@@ -141,9 +141,9 @@ __device__ __forceinline__ void step_group(const EnvParams& P, const float* acti
     }
     if (l < 7) mimp = ARM_FORCE * PHYSICS_DT;          /* kuka.py:282-290 */
     bool ok = true;
-    for (int s = 0; s < SIM_STEPS && ok; s++) {        /* kuka.py:223-225 */
+    for (int s = 0; s < RUN_SIM_STEPS && ok; s++) {        /* kuka.py:223-225 */
         float tau = -c.jdamp() * qd;                   /* joint damping latched per stepSimulation */
-        for (int ss = 0; ss < SUBSTEPS && ok; ss++) ok = substep_free(P, c, q, qd, tau, mtarget, mimp);
+        for (int ss = 0; ss < RUN_SUBSTEPS && ok; ss++) ok = substep_free(P, c, q, qd, tau, mtarget, mimp);
     }
     PMGP_T(8);
 #ifdef PMG_PROFILE

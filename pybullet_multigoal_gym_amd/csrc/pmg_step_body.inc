@@ -1101,7 +1101,7 @@ __device__ __forceinline__ void helper_wave_loop(const EnvParams& P, ContactLds<
     LaneConst c;                                            /* (wavefront 0 filled the table before its first barrier A) */
     c.st = &lcs;
     c.col = l < NJ ? l : NJ - 1;
-    for (int s = 0; s < SIM_STEPS * SUBSTEPS; s++) {
+    for (int s = 0; s < RUN_SIM_STEPS * RUN_SUBSTEPS; s++) {
         __syncthreads();                                    /* A: the substep's joint angles are in L.qd */
         /* Round 6: this wavefront runs its OWN forward kinematics from the joint angles (the same fk() on the same numbers as
          * wavefront 0's: identical frames) and publishes the frames itself, instead of waiting for wavefront 0's forward kinematics
@@ -1133,7 +1133,7 @@ __device__ __forceinline__ void helper_wave_loop(const EnvParams& P, ContactLds<
 template <int NB, int MAXC, int CYL>
 __device__ __forceinline__ void spec_wave_loop(const EnvParams& P, ContactLds<NB, MAXC>& L, const LaneTabStore& lcs, SpecLds<CYL>& sp)
 {
-    for (int s = 0; s < SIM_STEPS * SUBSTEPS; s++) {
+    for (int s = 0; s < RUN_SIM_STEPS * RUN_SUBSTEPS; s++) {
         __syncthreads();                                    /* A */
         SpecFk fk;
         spec_fk<CYL>(sp, L.qd, fk);
@@ -1480,9 +1480,9 @@ __device__ __forceinline__ bool step_env_core(const EnvParams& P, const float* a
     WV::lds_sync();
     PMG_TICK(5);
     bool ok = true;
-    for (int s = 0; s < SIM_STEPS && ok; s++) {  /* kuka.py:223-225 */
+    for (int s = 0; s < RUN_SIM_STEPS && ok; s++) {  /* kuka.py:223-225 */
         float tau = -c.jdamp() * qd;         /* joint damping latched per stepSimulation */
-        for (int ss = 0; ss < SUBSTEPS && ok; ss++) ok = substep<NB, MAXC, CYL, TWO, SPEC>(P, L, c, q, qd, tau, mtarget, mimp, ncmax, sp);
+        for (int ss = 0; ss < RUN_SUBSTEPS && ok; ss++) ok = substep<NB, MAXC, CYL, TWO, SPEC>(P, L, c, q, qd, tau, mtarget, mimp, ncmax, sp);
     }
     PMG_TICK(6);
     if (!ok || !live) return ok;

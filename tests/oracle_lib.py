@@ -248,6 +248,50 @@ class FloorOracle(OracleEnv):
             set_prior('state_f32_per_substep', 0.0)
 
 
+MAX_CONTACTS, MAX_SOLVER_ITERS = 64, 8      # PMGO_MAX_CONTACTS, PMGO_MAX_SOLVER_ITERS (oracle/pmg_oracle.h)
+
+
+class SubstepOracle(OracleEnv):
+    """The oracle running `substeps` substeps per env step instead of 5 x 20 (the `sim_steps` / `substeps` switches of
+    oracle/pmg_oracle.c: loop bounds only).  substeps=1 is the reference of the product's one-substep builds
+    (tests/test_substep_emulated.py, tests/test_gpu_substep.py); other counts carry a scene to the middle of an env step
+    (tests/substep_cases.py).  `priors`: further switches for the same call (the mutants of the harness's self-check).  The
+    switches are process-wide: on for one step() call, then back at their defaults -- in the build this env runs on."""
+
+    def __init__(self, task, num_envs, substeps=1, priors=None, **kw):
+        OracleEnv.__init__(self, task, num_envs, **kw)
+        self.f32 = bool(kw.get('f32', False))
+        self.switches = dict(priors or {}, sim_steps=1, substeps=substeps)
+
+    def step(self, actions):
+        before = {k: get_prior(k, self.f32) for k in self.switches}
+        for k, v in self.switches.items():
+            set_prior(k, v, self.f32)
+        try:
+            return OracleEnv.step(self, actions)
+        finally:
+            for k, v in before.items():
+                set_prior(k, v, self.f32)
+
+    def last_substep(self):
+        """Every env's last substep: dict(nc [N], a / b [N, 64] body ids per contact in solve order (-9 beyond nc), point_a
+        [N, 64, 3], distance / impulse [N, 64], iterations [N], residual [N, 8] (0 beyond the iterations run))"""
+        N = self.N
+        out = dict(nc=np.zeros(N, np.int32), a=np.full((N, MAX_CONTACTS), -9, np.int32), b=np.full((N, MAX_CONTACTS), -9, np.int32),
+                   point_a=np.zeros((N, MAX_CONTACTS, 3)), distance=np.zeros((N, MAX_CONTACTS)), impulse=np.zeros((N, MAX_CONTACTS)), iterations=np.zeros(N, np.int32),
+                   residual=np.zeros((N, MAX_SOLVER_ITERS)))
+        self.lib.pmgo_last_substep.restype = C.c_int
+        for i in range(N):
+            nc, it = C.c_int32(), C.c_int32()
+            a, b = np.zeros(MAX_CONTACTS, np.int32), np.zeros(MAX_CONTACTS, np.int32)
+            rc = self.lib.pmgo_last_substep(self.h, C.c_int(i), C.byref(nc), _fp(a), _fp(b), _fp(out['point_a'][i]), _fp(out['distance'][i]), _fp(out['impulse'][i]),
+                                            C.byref(it), _fp(out['residual'][i]))
+            assert rc == 0
+            out['nc'][i], out['iterations'][i] = nc.value, it.value
+            out['a'][i, :nc.value], out['b'][i, :nc.value] = a[:nc.value], b[:nc.value]
+        return out
+
+
 def cyl_box(cc, Rc, rad, hl, cb, Rb, hb, margin=0.002, f32=False):
     lib = load(f32)
     a = [np.ascontiguousarray(x, np.float64) for x in (cc, Rc, cb, Rb, hb)]
