@@ -357,7 +357,7 @@ int pmg_td_target_device(pmg_env* env, const pmg_mlp* actor_target, const pmg_ml
  * A row's delta, d_gx, d_ga and d_out do not depend on the batch it is in; dW and db depend on the row order and on nothing else; nothing
  * depends on the grid or the number of compute units; two calls on the same inputs give the same bits.
  * Known limit: the single chain over the batch costs B / 2 dependent matrix steps per tile of a dW.  That is the right trade for the
- * minibatches HER uses (256 to 4096 rows); a chunked reduction with its own normative order is later work.
+ * minibatches HER uses (256 to 4096 rows); pmg_mlp_grad_chunked_device below is the chunked reduction, with its own normative order.
  *
  * PMG_E_INVALID, with nothing launched: everything pmg_q_device rejects in the network and the row tables; d_a without a_dim >= 1 or the
  * reverse; x_dim + a_dim != width[0]; d_ga without d_a; both d_gout and d_target; gscale not finite; grads, d_gx, d_ga and d_out all
@@ -386,6 +386,29 @@ typedef struct pmg_mlp_grad {
 } pmg_mlp_grad;
 int64_t pmg_mlp_grad_work_floats(const pmg_mlp* mlp, int64_t batch);   /* < 0: invalid network / batch */
 int pmg_mlp_grad_device(pmg_env* env, const pmg_mlp* mlp, const pmg_mlp_grad* g);
+
+/* pmg_mlp_grad_chunked_device (normative), float32 throughout: pmg_mlp_grad_device with the batch reduction of dW / db cut
+ * into chunks of R = chunk_rows rows, so that ceil(B / R) times as many wavefronts run chains of R / 2 matrix steps instead of B / 2.
+ * Stream-ordered on the handle's stream, syncs nothing, writes only its outputs and d_work, touches no state of the handle.
+ * Forward, head, output delta, s_l, masks, d_gx, d_ga and d_out: pmg_mlp_grad_device above, to the letter.
+ * C = ceil(B / R) chunks; chunk c holds the rows c R ... min((c + 1) R, B) - 1.
+ *   P_c[j][k]:  acc = +0.0; acc = fmaf(delta_l[b][j], h_l[b][k], acc) for b ascending over chunk c.
+ *   Pb_c[j]:    acc = +0.0; acc = acc + delta_l[b][j] for b ascending over chunk c.
+ *   dW_l[j][k] = (...((P_0 + P_1) + P_2) ... + P_{C-1}): float32 additions, c ascending, one rounding each; db_l likewise from Pb_c.
+ * C == 1 (R >= B) is by definition pmg_mlp_grad_device: the same bits.  gscale is the caller's: nothing is rescaled per chunk.  dW and db
+ * depend on the row order and on R and on nothing else -- not on the grid or the number of compute units --, and two calls on the same
+ * inputs give the same bits.  Zeros compare by value, as above.
+ * Workspace: pmg_mlp_grad_chunked_work_floats(mlp, batch, chunk_rows) = pmg_mlp_grad_work_floats(mlp, batch), laid out as for
+ * pmg_mlp_grad_device, and for C > 1 behind it C x P floats of partials, P = the sum over the layers of (width[l] + 1) * width[l + 1] (a
+ * bias is counted for every layer).  With grads == NULL (input gradients only) nothing is reduced: pmg_mlp_grad_work_floats(mlp, batch)
+ * suffices.
+ * PMG_E_INVALID, with nothing launched: everything pmg_mlp_grad_device rejects; chunk_rows < 2 or odd (an even R keeps every chunk's
+ * first row even, so only the last chunk can end on a single row); more than PMG_GRAD_MAX_CHUNKS chunks (the partials of all chunks are
+ * formed by one launch, a workgroup per chunk and 32 x 32 tile of a dW_l; 65 535 chunks of the at most 256 tiles of a network stay below
+ * the 2^32 work-items of one grid); work_floats below the figure above.  batch == 0 is a successful no-op that leaves grads untouched. */
+#define PMG_GRAD_MAX_CHUNKS 65535
+int64_t pmg_mlp_grad_chunked_work_floats(const pmg_mlp* mlp, int64_t batch, int64_t chunk_rows);   /* < 0: invalid network / batch / chunk_rows */
+int pmg_mlp_grad_chunked_device(pmg_env* env, const pmg_mlp* mlp, const pmg_mlp_grad* g, int64_t chunk_rows);
 
 /* Adam and Polyak: one elementwise launch over the up to eight tensors of a network each.  `shape` supplies the widths and which layers
  * have a bias; its pointers are not dereferenced.

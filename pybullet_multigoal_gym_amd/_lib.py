@@ -103,7 +103,8 @@ class PmgLibrary:
                'pmg_norm_configure', 'pmg_norm_update_device', 'pmg_norm_update', 'pmg_norm_update_env_device', 'pmg_norm_read',
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
                'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
-               'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device']
+               'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
+               'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -125,6 +126,7 @@ class PmgLibrary:
             if name not in ('pmg_last_error', 'pmg_destroy'):
                 getattr(L, name).restype = C.c_int
         L.pmg_mlp_grad_work_floats.restype = C.c_int64
+        L.pmg_mlp_grad_chunked_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -402,6 +404,14 @@ class PmgHandle:
     def mlp_grad_device(self, mlp, grad):
         """forward with saved activations, then backward, of a grad_struct(); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_mlp_grad_device(self.h, C.byref(mlp), C.byref(grad)))
+
+    def mlp_grad_chunked_work_floats(self, mlp, batch, chunk_rows):
+        """floats of workspace pmg_mlp_grad_chunked_device needs for `batch` rows in chunks of `chunk_rows` (< 0: invalid)"""
+        return int(self.L.lib.pmg_mlp_grad_chunked_work_floats(C.byref(mlp), C.c_int64(batch), C.c_int64(chunk_rows)))
+
+    def mlp_grad_chunked_device(self, mlp, grad, chunk_rows):
+        """mlp_grad_device with dW / db reduced over chunks of `chunk_rows` rows (even, >= 2); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_grad_chunked_device(self.h, C.byref(mlp), C.byref(grad), C.c_int64(chunk_rows)))
 
     def mlp_adam_device(self, shape, param, grad, m, v, adam):
         """one Adam step on the tensors of `param` (params_struct()s, adam_struct()); stream-ordered, no host sync."""

@@ -2,21 +2,22 @@
 y = clip(r + gamma Q'(x', pi'(x'))) of a minibatch in one fused call.
 
 Host-side face of ``pmg_q_device`` and ``pmg_td_target_device`` (include/pmg.h); the update side -- gradients, Adam, Polyak
-(DESIGN.md 3.11) -- comes from ``optim.Trainable``, which ``Actor`` shares.  All arithmetic happens in the HIP library; this file uploads
+(DESIGN.md 3.11, 3.12) -- comes from ``optim.Trainable``, which ``Actor`` shares.  All arithmetic happens in the HIP library; this file uploads
 the network, validates shapes and moves buffers.  The weights live in buffers this object owns until ``close()`` (or the next ``load``).
 There is no learner class: one DDPG / HER update is this sequence of stream-ordered calls, with the online and the target networks in
 four objects (``actor, critic = env.actor, env.critic; actor_t, critic_t = Actor(env), Critic(env)``, all loaded) and nothing leaving the
 GPU:
 
     sa, sc = actor.adam_state(), critic.adam_state()                        # once: moments, a gradient buffer .g, t
-    work = max(actor.grad_work_floats(B), critic.grad_work_floats(B)); d_work = h.device_alloc(4 * work)
+    R = 256                    # chunk_rows of the two full gradients: 256 at B = 4096, 1024 at 65 536, None for B = 256
+    work = max(actor.grad_work_floats(B, R), critic.grad_work_floats(B, R)); d_work = h.device_alloc(4 * work)
     h.her_sample_device(rows, E, T, es, ts, B, ..., d_x=d_x, d_x_next=d_xn, d_action=d_a, d_reward=d_r, d_goal_achieved=d_ok)
     critic_t.td_target_device(actor_t, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, d_terminal=d_ok, batch=B)          # y
-    critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_a, a_dim=A, d_target=d_y, gscale=2.0 / B, grads=sc.g)          # d mean (Q - y)^2
+    critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_a, a_dim=A, d_target=d_y, gscale=2.0 / B, grads=sc.g, chunk_rows=R)   # d mean (Q - y)^2
     critic.adam_step_device(sc.g, sc, lr)
     h.mlp_forward_device(actor._loaded(), d_x, Dx, B, d_pi, A)                                                        # a = pi(x)
     critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_pi, a_dim=A, gscale=-1.0 / B, d_ga=d_ga)                       # d (-mean Q) / da
-    actor.grad_device(B, d_x, Dx, d_work, work, d_gout=d_ga, grads=sa.g)
+    actor.grad_device(B, d_x, Dx, d_work, work, d_gout=d_ga, grads=sa.g, chunk_rows=R)
     actor.adam_step_device(sa.g, sa, lr)
     actor_t.soft_update_from(actor, tau); critic_t.soft_update_from(critic, tau)
 """

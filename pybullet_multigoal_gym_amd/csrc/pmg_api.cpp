@@ -1103,11 +1103,9 @@ static int params_of(pmg_env* e, const PmgMlp& M, const pmg_mlp_params* p, bool 
     return PMG_OK;
 }
 
-int pmg_mlp_grad_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g)
+/* everything pmg_mlp_grad_device checks in its arguments but the size of the workspace -> M; 0 or PMG_E_INVALID */
+static int grad_args_of(pmg_env* e, const char* who, const pmg_mlp* mlp, const pmg_mlp_grad* g, PmgMlp& M)
 {
-    if (!e) return PMG_E_INVALID;
-    const char* who = "pmg_mlp_grad_device";
-    PmgMlp M;
     if (int rc = mlp_of(e, mlp, who, M)) return rc;
     if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
     if (g->struct_size != (int32_t)sizeof(pmg_mlp_grad)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_mlp_grad));
@@ -1127,13 +1125,19 @@ int pmg_mlp_grad_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g)
     if (g->x_stride < g->x_dim || (g->d_a && g->a_stride < g->a_dim) || (g->d_gout && g->gout_stride < A) || (g->d_target && g->target_stride < A) ||
         (g->d_gx && g->gx_stride < g->x_dim) || (g->d_ga && g->ga_stride < g->a_dim) || (g->d_out && g->out_stride < A))
         return fail(e, PMG_E_INVALID, "%s: a stride is smaller than its width", who);
-    const int64_t need = pmg_mlp_grad_work_floats(mlp, g->batch);
+    return PMG_OK;
+}
+/* the workspace of a checked call: `need` floats (< 0: the batch is too large) */
+static int grad_work_of(pmg_env* e, const char* who, const pmg_mlp_grad* g, int64_t need)
+{
     if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)g->batch);
     if (!g->d_work || g->work_floats < need) return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld < %lld", who, (long long)g->work_floats, (long long)need);
-    if (g->batch == 0) return PMG_OK;
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return PMG_OK;
+}
+/* the launcher's view of a checked call on M.B = g->batch rows, the workspace cut */
+static void grad_launch_args(const pmg_mlp_grad* g, PmgMlp& M, PmgGrad& G)
+{
     M.B = g->batch;
-    PmgGrad G;
     memset(&G, 0, sizeof(G));
     G.x = g->d_x; G.xs = g->x_stride; G.x_dim = g->x_dim; G.a = g->d_a; G.as = g->a_stride; G.a_dim = g->a_dim;
     G.gout = g->d_gout; G.gos = g->gout_stride; G.target = g->d_target; G.ts = g->target_stride; G.gscale = g->gscale;
@@ -1141,6 +1145,19 @@ int pmg_mlp_grad_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g)
     for (int l = 0; l < M.L && g->grads; l++) { G.dw[l] = g->grads->d_weight[l]; G.db[l] = M.b[l] ? g->grads->d_bias[l] : nullptr; }
     G.gx = g->d_gx; G.gxs = g->gx_stride; G.ga = g->d_ga; G.gas = g->ga_stride; G.out = g->d_out; G.os = g->out_stride;
     pmg_grad_work_layout(M, M.B, g->d_work, &G);
+}
+
+int pmg_mlp_grad_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_grad_device";
+    PmgMlp M;
+    if (int rc = grad_args_of(e, who, mlp, g, M)) return rc;
+    if (int rc = grad_work_of(e, who, g, pmg_mlp_grad_work_floats(mlp, g->batch))) return rc;
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgGrad G;
+    grad_launch_args(g, M, G);
     HIP_TRY(e, pmg_launch_mlp_grad(M, G, e->stream));
     return PMG_OK;
 }
@@ -1205,6 +1222,58 @@ int pmg_mlp_polyak_device(pmg_env* e, const pmg_mlp* source, const pmg_mlp_param
     PmgSegs T;
     segs_of(M, target, M.w, M.b, nullptr, nullptr, T);
     HIP_TRY(e, pmg_launch_polyak(T, tau, e->stream));
+    return PMG_OK;
+}
+
+/* ---- chunked batch reduction of dW / db ---- */
+/* P of the partials: a bias is counted for every layer, so the figure needs the widths alone */
+static int64_t grad_chunk_params(const pmg_mlp* mlp)
+{
+    int64_t P = 0;
+    for (int l = 0; l < mlp->num_layers; l++) P += ((int64_t)mlp->width[l] + 1) * mlp->width[l + 1];
+    return P;
+}
+int64_t pmg_mlp_grad_chunked_work_floats(const pmg_mlp* mlp, int64_t batch, int64_t chunk_rows)
+{
+    const int64_t base = pmg_mlp_grad_work_floats(mlp, batch);
+    if (base < 0 || chunk_rows < 2 || (chunk_rows & 1)) return -1;
+    const int64_t C = batch / chunk_rows + (batch % chunk_rows != 0);
+    if (C > PMG_GRAD_MAX_CHUNKS) return -1;
+    return C <= 1 ? base : base + C * grad_chunk_params(mlp);
+}
+
+int pmg_mlp_grad_chunked_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_grad* g, int64_t chunk_rows)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_grad_chunked_device";
+    PmgMlp M;
+    if (int rc = grad_args_of(e, who, mlp, g, M)) return rc;
+    if (chunk_rows < 2 || (chunk_rows & 1)) return fail(e, PMG_E_INVALID, "%s: chunk_rows %lld must be even and >= 2", who, (long long)chunk_rows);
+    const int64_t C = g->batch / chunk_rows + (g->batch % chunk_rows != 0);
+    if (C > PMG_GRAD_MAX_CHUNKS)
+        return fail(e, PMG_E_INVALID, "%s: batch %lld in chunks of %lld rows is %lld chunks, more than %d", who, (long long)g->batch, (long long)chunk_rows, (long long)C, PMG_GRAD_MAX_CHUNKS);
+    const bool chunked = g->grads && C > 1;
+    const int64_t base = pmg_mlp_grad_work_floats(mlp, g->batch);
+    if (int rc = grad_work_of(e, who, g, chunked ? pmg_mlp_grad_chunked_work_floats(mlp, g->batch, chunk_rows) : base)) return rc;
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgGrad G;
+    grad_launch_args(g, M, G);
+    if (!chunked) {                                                /* one chunk is the single chain; input gradients have no reduction */
+        HIP_TRY(e, pmg_launch_mlp_grad(M, G, e->stream));
+        return PMG_OK;
+    }
+    PmgSegs T;
+    segs_of(M, g->grads, g->grads->d_weight, g->grads->d_bias, nullptr, nullptr, T);
+    PmgGradChunks Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.R = chunk_rows; Q.C = C; Q.P = grad_chunk_params(mlp); Q.tiles = pmg_grad_w_tiles(M); Q.part = g->d_work + base;
+    for (int l = 0, n = 0; l < M.L; l++) {                          /* tensor n of T starts at T.end[n - 1] */
+        Q.pw[l] = Q.part + (n ? T.end[n - 1] : 0);
+        n++;
+        if (M.b[l]) { Q.pb[l] = Q.part + T.end[n - 1]; n++; }
+    }
+    HIP_TRY(e, pmg_launch_mlp_grad_chunked(M, G, Q, T, e->stream));
     return PMG_OK;
 }
 

@@ -107,6 +107,18 @@ struct PmgSegs {
     float* p[8]; const float* g[8]; float* m[8]; float* v[8];
 };
 struct PmgAdam { float beta1, beta2, omb1, omb2, step_size, rsc2, eps; };
+/* the chunked batch reduction of dW / db (pmg_mlp_grad_chunked_device), C >= 2 chunks of R rows (R even; the last chunk
+ * holds the rest).  part: [C][P] floats behind the layout of pmg_grad_work_layout, P = the network's parameters, chunk c's partial of
+ * every tensor in the flat order of T; pw[l] / pb[l]: where dW_l / db_l start in chunk 0's (pb[l] null without that bias); tiles =
+ * pmg_grad_w_tiles(M), the 32 x 32 tiles of all dW_l; T.p: the gradient tensors the merge writes.  G.grads != 0. */
+struct PmgGradChunks {
+    long long R, C, P;
+    int tiles;
+    float* part;
+    float* pw[4]; float* pb[4];
+};
+int pmg_grad_w_tiles(const PmgMlp& M);
+hipError_t pmg_launch_mlp_grad_chunked(const PmgMlp& M, const PmgGrad& G, const PmgGradChunks& Q, const PmgSegs& T, hipStream_t s);
 hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
 #endif

@@ -936,21 +936,22 @@ __device__ __forceinline__ void grad_w_mma(const float* __restrict__ delta, int 
     }
 #endif
 }
-/* the whole chain over the batch of one dW tile, rows ascending, and its stores.  Eight steps are written out, as in mlp_chain */
+/* the chain over the rows [lo, hi) of one dW tile, lo even, rows ascending, and its stores (the whole batch: lo = 0, hi = B).  Eight steps are
+ * written out, as in mlp_chain */
 template <bool BIAS>
-__device__ __forceinline__ void grad_w_tile(const float* __restrict__ delta, int J, int K, int jb, int k, const GradHCol& hf, long long B, int lane,
+__device__ __forceinline__ void grad_w_tile(const float* __restrict__ delta, int J, int K, int jb, int k, const GradHCol& hf, long long lo, long long hi, int lane,
                                             float* __restrict__ dw, float* __restrict__ db)
 {
     MlpAcc acc, accb;
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) { acc[reg] = 0.f; accb[reg] = 0.f; }
-    const long long B16 = B & ~15ll, Be = B & ~1ll;
-    for (long long b0 = 0; b0 < B16; b0 += 16) {
+    const long long n = hi - lo, B16 = lo + (n & ~15ll), Be = lo + (n & ~1ll);
+    for (long long b0 = lo; b0 < B16; b0 += 16) {
 #pragma unroll
         for (int u = 0; u < 16; u += 2) grad_w_mma<false, BIAS>(delta, J, jb, hf, b0 + u, lane, acc, accb);
     }
     for (long long b0 = B16; b0 < Be; b0 += 2) grad_w_mma<false, BIAS>(delta, J, jb, hf, b0, lane, acc, accb);
-    if (B & 1) grad_w_mma<true, BIAS>(delta, J, jb, hf, Be, lane, acc, accb);
+    if (n & 1) grad_w_mma<true, BIAS>(delta, J, jb, hf, Be, lane, acc, accb);
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
         const int j = jb + mlp_row(reg, lane);
@@ -959,11 +960,13 @@ __device__ __forceinline__ void grad_w_tile(const float* __restrict__ delta, int
         if (BIAS && (lane & 31) == 0) db[j] = accb[reg];
     }
 }
-/* one wavefront per 32 x 32 tile of a dW_l, the tiles of layer 0 first; the tiles of input strip 0 carry the bias sums of their units */
+/* tile `tile` of the network's dW tiles (the tiles of layer 0 first) over the rows [lo, hi) into dw[l] / db[l]; the tiles of input strip 0
+ * carry the bias sums of their units */
 template <class Src>
-__global__ void __launch_bounds__(64) pmg_k_mlp_grad_weights(Src S, PmgMlp M, PmgGrad G)
+__device__ __forceinline__ void grad_w_run(const Src& S, const PmgMlp& M, const PmgGrad& G, int tile, long long lo, long long hi,
+                                           float* const* dw, float* const* db, long long shift)
 {
-    int tile = (int)blockIdx.x, l = 0, tk = 0;
+    int l = 0, tk = 0;
     for (;; l++) {
         tk = (M.width[l] + 31) / 32;
         const int n = ((M.width[l + 1] + 31) / 32) * tk;
@@ -975,8 +978,14 @@ __global__ void __launch_bounds__(64) pmg_k_mlp_grad_weights(Src S, PmgMlp M, Pm
     GradHCol hf;
     if (l == 0) hf.p = mlp_column(S, kl, hf.stride);
     else { hf.p = G.wh[l] + kl; hf.stride = K; }
-    if (kb == 0 && G.db[l] != nullptr) grad_w_tile<true>(G.wd[l], J, K, jb, k, hf, M.B, lane, G.dw[l], G.db[l]);
-    else grad_w_tile<false>(G.wd[l], J, K, jb, k, hf, M.B, lane, G.dw[l], G.db[l]);
+    if (kb == 0 && db[l] != nullptr) grad_w_tile<true>(G.wd[l], J, K, jb, k, hf, lo, hi, lane, dw[l] + shift, db[l] + shift);
+    else grad_w_tile<false>(G.wd[l], J, K, jb, k, hf, lo, hi, lane, dw[l] + shift, db[l]);
+}
+/* one wavefront per 32 x 32 tile of a dW_l, ONE chain over the whole batch */
+template <class Src>
+__global__ void __launch_bounds__(64) pmg_k_mlp_grad_weights(Src S, PmgMlp M, PmgGrad G)
+{
+    grad_w_run(S, M, G, (int)blockIdx.x, 0, M.B, G.dw, G.db, 0);
 }
 long long pmg_grad_work_layout(const PmgMlp& M, long long B, float* work, PmgGrad* G)
 {
@@ -991,14 +1000,18 @@ long long pmg_grad_work_layout(const PmgMlp& M, long long B, float* work, PmgGra
     }
     return per_row * B;
 }
+int pmg_grad_w_tiles(const PmgMlp& M)
+{
+    int tiles = 0;
+    for (int l = 0; l < M.L; l++) tiles += ((M.width[l + 1] + 31) / 32) * ((M.width[l] + 31) / 32);
+    return tiles;
+}
 template <class Src>
 static void launch_mlp_grad(const Src& S, const PmgMlp& M, const PmgGrad& G, hipStream_t s)
 {
     hipLaunchKernelGGL((pmg_k_mlp_grad_rows<Src>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M, G);
     if (!G.grads) return;
-    int tiles = 0;
-    for (int l = 0; l < M.L; l++) tiles += ((M.width[l + 1] + 31) / 32) * ((M.width[l] + 31) / 32);
-    hipLaunchKernelGGL((pmg_k_mlp_grad_weights<Src>), dim3(tiles), dim3(64), 0, s, S, M, G);
+    hipLaunchKernelGGL((pmg_k_mlp_grad_weights<Src>), dim3(pmg_grad_w_tiles(M)), dim3(64), 0, s, S, M, G);
 }
 hipError_t pmg_launch_mlp_grad(const PmgMlp& M, const PmgGrad& G, hipStream_t s)
 {
@@ -1054,5 +1067,43 @@ hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s)
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s)
 {
     hipLaunchKernelGGL(pmg_k_polyak, dim3(seg_grid(T)), dim3(256), 0, s, T, tau);
+    return hipGetLastError();
+}
+
+/* The chunked batch reduction (pmg_mlp_grad_chunked_device, DESIGN.md 3.12): pmg_k_mlp_grad_rows as above, then pmg_k_mlp_grad_partials, one
+ * wavefront per (chunk, 32 x 32 tile of a dW_l) -- grad_w_run over the chunk's rows alone, chunk c's partial of every tensor at part + c P in
+ * the flat order of PmgSegs --, then pmg_k_mlp_grad_merge, a thread per parameter that adds its C partials in ascending c (consecutive
+ * addresses across the lanes) and stores the sum.  Stream order is the only synchronisation: no atomics, no counter.  The chains run
+ * R / 2 steps on tiles x C wavefronts where the single chain runs B / 2 on tiles. */
+template <class Src>
+__global__ void __launch_bounds__(64) pmg_k_mlp_grad_partials(Src S, PmgMlp M, PmgGrad G, PmgGradChunks Q)
+{
+    const long long c = (long long)(blockIdx.x / (unsigned)Q.tiles), lo = c * Q.R, hi = lo + Q.R < M.B ? lo + Q.R : M.B;
+    grad_w_run(S, M, G, (int)(blockIdx.x % (unsigned)Q.tiles), lo, hi, Q.pw, Q.pb, c * Q.P);
+}
+__global__ void __launch_bounds__(256) pmg_k_mlp_grad_merge(PmgSegs T, const float* __restrict__ part, long long C, long long P)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const float* __restrict__ p = part + i;
+        float acc = p[0];
+#pragma unroll 8
+        for (long long c = 1; c < C; c++) acc = acc + p[c * P];
+        const SegAt s = seg_at(T, i);
+        s.p[s.i] = acc;
+    }
+}
+template <class Src>
+static void launch_mlp_grad_chunked(const Src& S, const PmgMlp& M, const PmgGrad& G, const PmgGradChunks& Q, const PmgSegs& T, hipStream_t s)
+{
+    hipLaunchKernelGGL((pmg_k_mlp_grad_rows<Src>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M, G);
+    hipLaunchKernelGGL((pmg_k_mlp_grad_partials<Src>), dim3((unsigned)(Q.C * Q.tiles)), dim3(64), 0, s, S, M, G, Q);
+    hipLaunchKernelGGL(pmg_k_mlp_grad_merge, dim3(seg_grid(T)), dim3(256), 0, s, T, (const float*)Q.part, Q.C, Q.P);
+}
+hipError_t pmg_launch_mlp_grad_chunked(const PmgMlp& M, const PmgGrad& G, const PmgGradChunks& Q, const PmgSegs& T, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    if (G.a) launch_mlp_grad_chunked(MlpCatRows{G.x, G.xs, G.a, G.as, G.x_dim}, M, G, Q, T, s);
+    else launch_mlp_grad_chunked(MlpRawRows{G.x, G.xs}, M, G, Q, T, s);
     return hipGetLastError();
 }
