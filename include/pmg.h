@@ -424,6 +424,49 @@ int pmg_mlp_adam_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params
                         const pmg_mlp_params* m, const pmg_mlp_params* v, const pmg_adam* a);
 int pmg_mlp_polyak_device(pmg_env* env, const pmg_mlp* source, const pmg_mlp_params* target, float tau);
 
+/* pmg_policy_grad_device (normative), float32 throughout: the actor's half of a DDPG / HER update in one call -- the gradient of
+ *   gscale * sum_b Q(x[b], clip(pi(x[b]))) + l2scale / 2 * sum_b sum_j pi(x[b])[j]^2
+ * with respect to the actor's parameters, through the online critic.  HER's loss -mean Q + action_l2 * mean(pi^2) is gscale = -1 / B and
+ * l2scale = 2 * action_l2 / (B * A).  Stream-ordered on the handle's stream, syncs nothing, writes only its outputs and d_work, touches no
+ * state of the handle; neither network's weights are written.  Per row b, Dx = actor.width[0], A = actor.width[L]:
+ *   1. z = the actor's layer chain on x[b];  o[j] = actor.out_activation ? tanhf(z[j]) : z[j];  a[j] = fminf(fmaxf(o[j], -1), 1), the a' of
+ *      pmg_td_target_device.  d_out receives o, d_action receives a.
+ *   2. q = critic.out_activation(z_c), z_c = the critic's chain on the row x[b] | a.  d_q receives q.
+ *   3. The critic's backward is pmg_mlp_grad_device's with the constant head gscale and input gradients only:
+ *      delta = critic.out_activation ? gscale * fmaf(-q, q, 1.f) : gscale, then the transposed chains s_l and the masks;
+ *      ga[j] = s_0[Dx + j].  d_gaction receives ga.  No gradient of the critic's parameters is formed.
+ *   4. g[j] = fmaf(l2scale, o[j], (o[j] >= -1.f && o[j] <= 1.f) ? ga[j] : +0.0f): the clip's derivative, inclusive at +-1 as torch.clamp's is; a
+ *      NaN o takes the +0.0 branch; the L2 term acts on the unclipped o.
+ *   5. delta_{L-1} = actor.out_activation ? g * fmaf(-o, o, 1.f) : g, and from there dW_l and db_l of the actor exactly as pmg_mlp_grad_device
+ *      (chunk_rows == 0) or pmg_mlp_grad_chunked_device (chunk_rows >= 2, even) forms them from d_gout = g.
+ * So the call equals, bit for bit with zeros compared by value, pmg_mlp_forward_device(actor) -> a = clip(o) on the host ->
+ * pmg_mlp_grad_device(critic, x | a, constant head, d_ga, d_out) -> g on the host -> pmg_mlp_grad[_chunked]_device(actor, d_gout = g).
+ * A row's a, o, q and ga do not depend on the batch it is in; dW and db depend on the row order and on chunk_rows and on nothing else;
+ * nothing depends on the grid; two calls on the same inputs give the same bits.
+ * grads == NULL: steps 4 and 5 do not run and d_work is not touched.  Workspace: pmg_policy_grad_work_floats(actor, critic, batch, chunk_rows)
+ * = pmg_mlp_grad_work_floats(actor, batch) for chunk_rows == 0, pmg_mlp_grad_chunked_work_floats(actor, batch, chunk_rows) otherwise, laid
+ * out as those calls lay it out; while the critic runs, o is kept where the actor's delta_{L-1} will be.
+ * PMG_E_INVALID, with nothing launched: everything pmg_td_target_device rejects in the pair of networks (critic.width[0] != Dx + A,
+ * critic.width[L] != 1, a bad network); gscale or l2scale not finite; grads, d_action, d_out, d_q and d_gaction all NULL; a grads tensor
+ * that is NULL where the actor has that tensor, or a bias gradient where it has no bias; d_x NULL; d_work NULL or work_floats too small; a
+ * float pointer off 4 bytes; a stride below its width; batch < 0; chunk_rows negative, 1 or odd, or more than PMG_GRAD_MAX_CHUNKS chunks; a
+ * wrong struct_size.  batch == 0 is a successful no-op that leaves grads untouched. */
+typedef struct pmg_policy_grad {
+    int32_t struct_size, reserved;
+    float gscale;                        /* finite; -1 / B for -mean Q */
+    float l2scale;                       /* finite; 2 * action_l2 / (B * A) for action_l2 * mean(o^2); 0: no L2 term */
+    int64_t batch;
+    const float* d_x; int64_t x_stride;            /* [B, Dx] */
+    const pmg_mlp_params* grads;         /* the ACTOR's dW / db, overwritten; NULL: the outputs below only */
+    float* d_action; int64_t action_stride;        /* [B, A] or NULL: a = clip(o) */
+    float* d_out; int64_t out_stride;              /* [B, A] or NULL: o, unclipped */
+    float* d_q;                                    /* [B] or NULL: Q(x, a) of the online critic */
+    float* d_gaction; int64_t gaction_stride;      /* [B, A] or NULL: ga = dLoss / da in front of the clip and the L2 term */
+    float* d_work; int64_t work_floats;  /* scratch, at least pmg_policy_grad_work_floats(actor, critic, batch, chunk_rows) */
+} pmg_policy_grad;
+int64_t pmg_policy_grad_work_floats(const pmg_mlp* actor, const pmg_mlp* critic, int64_t batch, int64_t chunk_rows);   /* chunk_rows 0: one chain; < 0: invalid */
+int pmg_policy_grad_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

@@ -78,6 +78,13 @@ class PmgMlpGrad(C.Structure):
                 ('d_out', C.c_void_p), ('out_stride', C.c_int64), ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
 
 
+class PmgPolicyGrad(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gscale', C.c_float), ('l2scale', C.c_float), ('batch', C.c_int64),
+                ('d_x', C.c_void_p), ('x_stride', C.c_int64), ('grads', C.POINTER(PmgMlpParams)), ('d_action', C.c_void_p), ('action_stride', C.c_int64),
+                ('d_out', C.c_void_p), ('out_stride', C.c_int64), ('d_q', C.c_void_p), ('d_gaction', C.c_void_p), ('gaction_stride', C.c_int64),
+                ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
+
+
 class PmgAdam(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
                 ('step', C.c_int64)]
@@ -104,7 +111,7 @@ class PmgLibrary:
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
                'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
                'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
-               'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device']
+               'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -127,6 +134,7 @@ class PmgLibrary:
                 getattr(L, name).restype = C.c_int
         L.pmg_mlp_grad_work_floats.restype = C.c_int64
         L.pmg_mlp_grad_chunked_work_floats.restype = C.c_int64
+        L.pmg_policy_grad_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -412,6 +420,21 @@ class PmgHandle:
     def mlp_grad_chunked_device(self, mlp, grad, chunk_rows):
         """mlp_grad_device with dW / db reduced over chunks of `chunk_rows` rows (even, >= 2); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_mlp_grad_chunked_device(self.h, C.byref(mlp), C.byref(grad), C.c_int64(chunk_rows)))
+
+    @staticmethod
+    def policy_grad_struct(batch, d_x, x_stride, d_work, work_floats, gscale, l2scale=0.0, grads=None, d_action=None, action_stride=0, d_out=None,
+                           out_stride=0, d_q=None, d_gaction=None, gaction_stride=0):
+        """pmg_policy_grad from device pointers (integers or None); grads: a params_struct() or None (it must outlive the call)."""
+        return PmgPolicyGrad(C.sizeof(PmgPolicyGrad), 0, gscale, l2scale, batch, d_x, x_stride, C.pointer(grads) if grads is not None else None,
+                             d_action, action_stride, d_out, out_stride, d_q, d_gaction, gaction_stride, d_work, work_floats)
+
+    def policy_grad_work_floats(self, actor, critic, batch, chunk_rows=0):
+        """floats of workspace pmg_policy_grad_device needs (chunk_rows 0: one chain over the batch; < 0: invalid)"""
+        return int(self.L.lib.pmg_policy_grad_work_floats(C.byref(actor), C.byref(critic), C.c_int64(batch), C.c_int64(chunk_rows)))
+
+    def policy_grad_device(self, actor, critic, grad, chunk_rows=0):
+        """the actor's gradient through the critic, L2 and clip terms included, of a policy_grad_struct(); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_policy_grad_device(self.h, C.byref(actor), C.byref(critic), C.byref(grad), C.c_int64(chunk_rows)))
 
     def mlp_adam_device(self, shape, param, grad, m, v, adam):
         """one Adam step on the tensors of `param` (params_struct()s, adam_struct()); stream-ordered, no host sync."""

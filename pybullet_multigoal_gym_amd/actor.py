@@ -1,6 +1,7 @@
 """The actor of a goal-conditioned learner on the device: a small MLP and DDPG / HER's exploration on its output.
 
-Host-side face of ``pmg_mlp_forward_device`` and ``pmg_act_env_device`` (include/pmg.h).  All arithmetic happens
+Host-side face of ``pmg_mlp_forward_device``, ``pmg_act_env_device`` (include/pmg.h) and ``pmg_policy_grad_device``, the
+actor's half of an update through the critic in one call.  All arithmetic happens
 in the HIP library; this file uploads the network, validates shapes and moves buffers.  The library keeps no learner state: the
 weights live in buffers this object owns until ``close()`` (or the next ``load``).  A device-resident rollout is two
 stream-ordered calls per step and nothing leaves the GPU:
@@ -13,7 +14,7 @@ stream-ordered calls per step and nothing leaves the GPU:
 import numpy as np
 
 from ._lib import PMG_NORM_OBSERVATION, PMG_NORM_POLICY_STATE
-from .optim import Trainable
+from .optim import ParamBuffers, Trainable
 
 KINDS = {'observation': PMG_NORM_OBSERVATION, 'policy_state': PMG_NORM_POLICY_STATE}
 ACTIVATIONS = {'identity': 0, 'tanh': 1}
@@ -126,6 +127,84 @@ class Actor(Trainable):
         finally:
             h.device_free(d_out)
         return out
+
+    def _online_critic(self, critic):
+        from .critic import Critic
+        if not isinstance(critic, Critic):
+            raise ValueError('critic must be a Critic (whose loaded network is the online critic), not %r' % (type(critic),))
+        mlp = critic._loaded()
+        if self.widths[0] + self.widths[-1] != critic.widths[0]:
+            raise ValueError('the actor maps %d -> %d, the critic takes %d inputs' % (self.widths[0], self.widths[-1], critic.widths[0]))
+        return mlp
+
+    def policy_grad_work_floats(self, critic, batch, chunk_rows=None):
+        """floats of workspace ``policy_grad_device`` needs for ``batch`` rows (with ``chunk_rows``: for the chunked reduction)"""
+        mlp = self._loaded()
+        chunk_rows = self._chunk_rows(chunk_rows)
+        return self._h.policy_grad_work_floats(mlp, self._online_critic(critic), int(batch), chunk_rows or 0)
+
+    def policy_grad_device(self, critic, batch, d_x, d_work, work_floats, gscale, l2scale=0.0, grads=None, d_action=None, d_out=None, d_q=None,
+                           d_gaction=None, x_stride=None, chunk_rows=None):
+        """The actor's half of an update in one call (pmg_policy_grad_device): the gradient of
+        ``gscale * sum Q(x, clip(pi(x))) + l2scale / 2 * sum pi(x)^2`` with respect to this network's parameters, through ``critic``, from
+        d_x [batch, Dx] in device memory.  HER's ``-mean Q + action_l2 * mean(pi^2)`` is ``gscale = -1 / B``, ``l2scale = 2 * action_l2 / (B * A)``.
+        ``grads``: a ParamBuffers that receives dW / db, or None (the outputs alone); d_action = clip(pi(x)) [batch, A], d_out = pi(x)
+        unclipped, d_q = Q [batch] and d_gaction = dLoss / da [batch, A] are optional, contiguous.  ``chunk_rows``: as in ``grad_device``.
+        On the handle's stream, no host sync."""
+        mlp, A = self._loaded(), self.widths[-1]
+        cmlp = self._online_critic(critic)
+        chunk_rows = self._chunk_rows(chunk_rows)
+        g = self._h.policy_grad_struct(int(batch), d_x, self.widths[0] if x_stride is None else x_stride, d_work, int(work_floats), float(gscale),
+                                       float(l2scale), None if grads is None else grads.struct, d_action, A, d_out, A, d_q, d_gaction, A)
+        self._h.policy_grad_device(mlp, cmlp, g, chunk_rows or 0)
+
+    def policy_grad(self, critic, x, gscale, l2scale=0.0, grads=True, chunk_rows=None):
+        """x [B, Dx] -> dict(dW, db: lists per layer, or None with ``grads=False``; action [B, A] = clip(pi(x)); out [B, A] = pi(x); q [B];
+        gaction [B, A] = dLoss / da).  gscale, l2scale, chunk_rows: as in ``policy_grad_device``."""
+        self._loaded()
+        self._online_critic(critic)
+        chunk_rows = self._chunk_rows(chunk_rows)
+        h, Dx, A = self._h, self.widths[0], self.widths[-1]
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 2 or x.shape[1] != Dx:
+            raise ValueError('x %s must be [B, %d]' % (x.shape, Dx))
+        if not np.isfinite(gscale) or not np.isfinite(l2scale):
+            raise ValueError('gscale %r and l2scale %r must be finite' % (gscale, l2scale))
+        B = x.shape[0]
+        res = {'dW': None, 'db': None, 'action': np.empty((B, A), np.float32), 'out': np.empty((B, A), np.float32), 'q': np.empty(B, np.float32),
+               'gaction': np.empty((B, A), np.float32)}
+        has_bias = [bool(self._mlp.d_bias[l]) for l in range(len(self.widths) - 1)]
+        if B == 0:
+            if grads:
+                res['dW'] = [np.zeros((self.widths[l + 1], self.widths[l]), np.float32) for l in range(len(has_bias))]
+                res['db'] = [np.zeros(self.widths[l + 1], np.float32) if keep else None for l, keep in enumerate(has_bias)]
+            return res
+        ptrs, bufs = [], None
+        try:
+            def room(arr):
+                ptrs.append(h.device_alloc(arr.nbytes))
+                return ptrs[-1]
+            d_x = room(x)
+            h.upload(d_x, x)
+            outs = [(res[k], room(res[k])) for k in ('action', 'out', 'q', 'gaction')]
+            work = self.policy_grad_work_floats(critic, B, chunk_rows if grads else None)
+            d_work = h.device_alloc(4 * max(work, 1))
+            ptrs.append(d_work)
+            if grads:
+                bufs = ParamBuffers(h, self.widths, has_bias)
+            self.policy_grad_device(critic, B, d_x, d_work, work, gscale, l2scale, bufs, outs[0][1], outs[1][1], outs[2][1], outs[3][1],
+                                    chunk_rows=chunk_rows)
+            h.sync()
+            for arr, p in outs:
+                h.download(arr, p)
+            if grads:
+                res['dW'], res['db'] = bufs.download()
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+            if bufs is not None:
+                bufs.close()
+        return res
 
     def close(self):
         """Free the uploaded network and the Adam states made for it."""

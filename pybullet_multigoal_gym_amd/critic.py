@@ -10,16 +10,19 @@ GPU:
 
     sa, sc = actor.adam_state(), critic.adam_state()                        # once: moments, a gradient buffer .g, t
     R = 256                    # chunk_rows of the two full gradients: 256 at B = 4096, 1024 at 65 536, None for B = 256
-    work = max(actor.grad_work_floats(B, R), critic.grad_work_floats(B, R)); d_work = h.device_alloc(4 * work)
+    work = max(actor.policy_grad_work_floats(critic, B, R), critic.grad_work_floats(B, R)); d_work = h.device_alloc(4 * work)
     h.her_sample_device(rows, E, T, es, ts, B, ..., d_x=d_x, d_x_next=d_xn, d_action=d_a, d_reward=d_r, d_goal_achieved=d_ok)
     critic_t.td_target_device(actor_t, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, d_terminal=d_ok, batch=B)          # y
     critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_a, a_dim=A, d_target=d_y, gscale=2.0 / B, grads=sc.g, chunk_rows=R)   # d mean (Q - y)^2
     critic.adam_step_device(sc.g, sc, lr)
-    h.mlp_forward_device(actor._loaded(), d_x, Dx, B, d_pi, A)                                                        # a = pi(x)
-    critic.grad_device(B, d_x, Dx, d_work, work, d_a=d_pi, a_dim=A, gscale=-1.0 / B, d_ga=d_ga)                       # d (-mean Q) / da
-    actor.grad_device(B, d_x, Dx, d_work, work, d_gout=d_ga, grads=sa.g, chunk_rows=R)
+    actor.policy_grad_device(critic, B, d_x, d_work, work, gscale=-1.0 / B, l2scale=2.0 * action_l2 / (B * A), grads=sa.g, chunk_rows=R)
     actor.adam_step_device(sa.g, sa, lr)
     actor_t.soft_update_from(actor, tau); critic_t.soft_update_from(critic, tau)
+
+The actor's line is the whole actor loss of HER, ``-mean Q(x, clip(pi(x))) + action_l2 * mean(pi(x)^2)``, in one call: the
+call differentiates ``gscale * sum Q + l2scale / 2 * sum pi^2``, so ``gscale = -1 / B`` carries the mean over the batch and
+``l2scale = 2 * action_l2 / (B * A)`` the mean over the B * A outputs and the 2 of the square's derivative; ``l2scale = 0`` is plain DDPG.
+The gradient is zero where the clip is active, and the L2 term acts on the unclipped output.
 """
 import numpy as np
 

@@ -1277,6 +1277,77 @@ int pmg_mlp_grad_chunked_device(pmg_env* e, const pmg_mlp* mlp, const pmg_mlp_gr
     return PMG_OK;
 }
 
+/* ---- the actor's half of an update in one call ---- */
+/* the workspace is the actor's: pmg_mlp_grad_work_floats, or with chunk_rows the chunked figure */
+int64_t pmg_policy_grad_work_floats(const pmg_mlp* actor, const pmg_mlp* critic, int64_t batch, int64_t chunk_rows)
+{
+    if (pmg_mlp_grad_work_floats(actor, batch) < 0 || pmg_mlp_grad_work_floats(critic, batch) < 0) return -1;
+    if (critic->width[0] != actor->width[0] + actor->width[actor->num_layers] || critic->width[critic->num_layers] != 1) return -1;
+    if (chunk_rows == 0) return pmg_mlp_grad_work_floats(actor, batch);
+    return pmg_mlp_grad_chunked_work_floats(actor, batch, chunk_rows);
+}
+
+int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_policy_grad_device";
+    PmgMlp P, Q;
+    if (int rc = mlp_of(e, actor, "pmg_policy_grad_device (actor)", P)) return rc;
+    if (int rc = mlp_of(e, critic, "pmg_policy_grad_device (critic)", Q)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L];
+    if (int rc = critic_of(e, Q, Dx + A, who)) return rc;
+    if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
+    if (g->struct_size != (int32_t)sizeof(pmg_policy_grad)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_policy_grad));
+    if (g->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)g->batch);
+    if (!g->d_x) return fail(e, PMG_E_INVALID, "%s: d_x is null", who);
+    if (!std::isfinite(g->gscale) || !std::isfinite(g->l2scale)) return fail(e, PMG_E_INVALID, "%s: gscale %g or l2scale %g is not finite", who, (double)g->gscale, (double)g->l2scale);
+    if (!g->grads && !g->d_action && !g->d_out && !g->d_q && !g->d_gaction)
+        return fail(e, PMG_E_INVALID, "%s: grads, d_action, d_out, d_q and d_gaction are all null: nothing to do", who);
+    if (g->grads) if (int rc = params_of(e, P, g->grads, false, who, "grads")) return rc;
+    if ((((size_t)g->d_x | (size_t)g->d_action | (size_t)g->d_out | (size_t)g->d_q | (size_t)g->d_gaction | (size_t)g->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (g->x_stride < Dx || (g->d_action && g->action_stride < A) || (g->d_out && g->out_stride < A) || (g->d_gaction && g->gaction_stride < A))
+        return fail(e, PMG_E_INVALID, "%s: a stride is smaller than its width", who);
+    if (chunk_rows < 0 || chunk_rows == 1 || (chunk_rows & 1)) return fail(e, PMG_E_INVALID, "%s: chunk_rows %lld must be 0 (one chain) or even and >= 2", who, (long long)chunk_rows);
+    const int64_t C = chunk_rows ? g->batch / chunk_rows + (g->batch % chunk_rows != 0) : 1;
+    if (C > PMG_GRAD_MAX_CHUNKS)
+        return fail(e, PMG_E_INVALID, "%s: batch %lld in chunks of %lld rows is %lld chunks, more than %d", who, (long long)g->batch, (long long)chunk_rows, (long long)C, PMG_GRAD_MAX_CHUNKS);
+    const bool chunked = g->grads && C > 1;
+    const int64_t base = pmg_mlp_grad_work_floats(actor, g->batch);
+    const int64_t need = chunked ? pmg_mlp_grad_chunked_work_floats(actor, g->batch, chunk_rows) : base;
+    if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)g->batch);
+    if (!g->d_work || g->work_floats < need) return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld < %lld", who, (long long)g->work_floats, (long long)need);
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = Q.B = g->batch;
+    PmgGrad G;
+    memset(&G, 0, sizeof(G));
+    G.x = g->d_x; G.xs = g->x_stride; G.x_dim = Dx;
+    G.grads = g->grads ? 1 : 0;
+    for (int l = 0; l < P.L && g->grads; l++) { G.dw[l] = g->grads->d_weight[l]; G.db[l] = P.b[l] ? g->grads->d_bias[l] : nullptr; }
+    G.out = g->d_out; G.os = g->out_stride;
+    pmg_grad_work_layout(P, P.B, g->d_work, &G);
+    PmgPolicy X;
+    X.gscale = g->gscale; X.l2scale = g->l2scale;
+    X.action = g->d_action; X.as = g->action_stride; X.q = g->d_q; X.ga = g->d_gaction; X.gas = g->gaction_stride;
+    if (!chunked) {
+        HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, nullptr, nullptr, e->stream));
+        return PMG_OK;
+    }
+    PmgSegs T;
+    segs_of(P, g->grads, g->grads->d_weight, g->grads->d_bias, nullptr, nullptr, T);
+    PmgGradChunks K;
+    memset(&K, 0, sizeof(K));
+    K.R = chunk_rows; K.C = C; K.P = grad_chunk_params(actor); K.tiles = pmg_grad_w_tiles(P); K.part = g->d_work + base;
+    for (int l = 0, n = 0; l < P.L; l++) {                          /* tensor n of T starts at T.end[n - 1] */
+        K.pw[l] = K.part + (n ? T.end[n - 1] : 0);
+        n++;
+        if (P.b[l]) { K.pb[l] = K.part + T.end[n - 1]; n++; }
+    }
+    HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, &K, &T, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

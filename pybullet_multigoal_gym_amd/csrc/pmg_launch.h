@@ -119,6 +119,18 @@ struct PmgGradChunks {
 };
 int pmg_grad_w_tiles(const PmgMlp& M);
 hipError_t pmg_launch_mlp_grad_chunked(const PmgMlp& M, const PmgGrad& G, const PmgGradChunks& Q, const PmgSegs& T, hipStream_t s);
+/* the actor's half of an update in one call (pmg_policy_grad_device), validated by the caller.  actor.B = critic.B rows of
+ * G.x [B, actor.width[0]]; G carries the ACTOR's arguments as for pmg_launch_mlp_grad (out = o unclipped, grads, dw / db, wh / wd cut by
+ * pmg_grad_work_layout(actor); a, gout, target, gx, ga null); X: a = clip(o) [B, A] at as, q [B], ga = dLoss / da [B, A] at gas (any may be
+ * null).  Q / T: the chunked reduction of the actor's dW / db as for pmg_launch_mlp_grad_chunked, or both null: one chain. */
+struct PmgPolicy {
+    float gscale, l2scale;
+    float* action; long long as;
+    float* q;
+    float* ga; long long gas;
+};
+hipError_t pmg_launch_policy_grad(const PmgMlp& actor, const PmgMlp& critic, const PmgGrad& G, const PmgPolicy& X, const PmgGradChunks* Q,
+                                  const PmgSegs* T, hipStream_t s);
 hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
 #endif

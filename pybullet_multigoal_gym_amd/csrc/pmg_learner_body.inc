@@ -1,6 +1,6 @@
 /* pmg_learner_body.inc -- the learner-side kernels and their launchers (included by pmg_kernels.hip): rewards of [B, G] batches,
- * the running normaliser, policy-input rows, HER minibatches, the actor forward, the critic / TD target, and back-propagation, Adam and
- * Polyak (DESIGN.md 3.6-3.11).  None of them touches EnvParams.  What two kernels share has ONE definition, so that they agree bit for bit
+ * the running normaliser, policy-input rows, HER minibatches, the actor forward, the critic / TD target, back-propagation, Adam and
+ * Polyak, and the actor's gradient through the critic in one call (DESIGN.md 3.6-3.13).  None of them touches EnvParams.  What two kernels share has ONE definition, so that they agree bit for bit
  * by construction: reward_of, sq_dist, policy_norm, flat_sweep, mlp_gather, mlp_layers, mlp_mma / mlp_chain. */
 /* distance, threshold, binary -> reward value and flag: the one definition (all three reward kernels and pmg_k_her_draw) */
 __device__ __forceinline__ float reward_of(float d, float thr, int binary, unsigned char& ok)
@@ -1105,5 +1105,186 @@ hipError_t pmg_launch_mlp_grad_chunked(const PmgMlp& M, const PmgGrad& G, const 
     if (M.B <= 0) return hipSuccess;
     if (G.a) launch_mlp_grad_chunked(MlpCatRows{G.x, G.xs, G.a, G.as, G.x_dim}, M, G, Q, T, s);
     else launch_mlp_grad_chunked(MlpRawRows{G.x, G.xs}, M, G, Q, T, s);
+    return hipGetLastError();
+}
+
+/* The actor's half of an update in one call (pmg_policy_grad_device, DESIGN.md 3.13): the actor's forward, the critic's forward on x | clip(o),
+ * the critic's input gradient, the L2 / clip head and the actor's transposed layers on ONE tile -- pmg_k_td_target's hand-over on the way
+ * forward, its mirror on the way back --, then the weights kernel of 3.11 (or the partials / merge pair of 3.12), unchanged, on the actor's
+ * workspace.  While the critic owns the tile, o lives in the workspace slot of the actor's delta_{L-1}: thread (row, unit) of the hand-over
+ * writes it, the same thread of the hand-back reads it and overwrites it with delta_{L-1}, so no ordering between threads is involved.
+ * Without grads the actor's backward does not run, o is not needed behind the hand-over and the workspace is not touched. */
+/* mlp_layers_saved for a network of which nothing is saved (the critic of pmg_k_policy_grad_rows): the same chains on the same tile and the
+ * lane's 2 x 16 signs per hidden layer in m1 / m2 / m3, bit for bit as there */
+__device__ __forceinline__ void mlp_layers_masked(float* tile, const PmgMlp& M, int lane, int wave, int col, unsigned int& m1, unsigned int& m2,
+                                                  unsigned int& m3)
+{
+#pragma unroll 1
+    for (int l = 0; l < M.L; l++) {
+        const int K = M.width[l], Nn = M.width[l + 1];
+        const float* __restrict__ W = M.w[l];
+        const float* __restrict__ bias = M.b[l];
+        const int u0 = 32 * wave + col, u1 = u0 + 128;
+        const bool live0 = u0 < Nn, live1 = u1 < Nn, strip0 = 32 * wave < Nn, strip1 = 32 * wave + 128 < Nn;
+        const float* w0 = W + (long long)(live0 ? u0 : 0) * K;
+        const float* w1 = W + (long long)(live1 ? u1 : 0) * K;
+        const float b0 = bias ? bias[live0 ? u0 : 0] : 0.f, b1 = bias ? bias[live1 ? u1 : 0] : 0.f;
+        MlpAcc acc0, acc1;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { acc0[reg] = b0; acc1[reg] = b1; }
+        if (strip1) mlp_chain<2>(tile, w0, w1, K, lane, acc0, acc1);
+        else if (strip0) mlp_chain<1>(tile, w0, w1, K, lane, acc0, acc1);
+        const bool hidden = l + 1 < M.L;
+        unsigned int mask = 0;
+        __syncthreads();                                         /* every wavefront has read the layer's input */
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int r = mlp_row(reg, lane);
+            if (strip0) {
+                tile[r * MLP_LD + u0] = live0 ? (hidden ? fmaxf(acc0[reg], 0.f) : acc0[reg]) : 0.f;
+                mask |= (unsigned int)(live0 && acc0[reg] > 0.f) << reg;
+            }
+            if (strip1) {
+                tile[r * MLP_LD + u1] = live1 ? (hidden ? fmaxf(acc1[reg], 0.f) : acc1[reg]) : 0.f;
+                mask |= (unsigned int)(live1 && acc1[reg] > 0.f) << (16 + reg);
+            }
+        }
+        if (l == 0) m1 = mask; else if (l == 1) m2 = mask; else if (l == 2) m3 = mask;
+        __syncthreads();
+    }
+}
+/* mlp_backward for that network: the transposed layers L-1 ... 1 on the tile, nothing saved; then layer 0, of which only the action columns
+ * [Dx, Dx + A) are wanted: s_0 of the 32-unit strips that hold any of them goes to the tile at its own columns (units past the width: +0.0)
+ * and, when asked, to ga; the strips that hold none run no chain.  Ends behind a barrier */
+__device__ __forceinline__ void mlp_backward_action(float* tile, const PmgMlp& M, int Dx, float* __restrict__ ga, long long gas, long long row0,
+                                                    int lane, int wave, int col, unsigned int m1, unsigned int m2, unsigned int m3)
+{
+#pragma unroll 1
+    for (int l = M.L - 1; l >= 0; l--) {
+        const int J = M.width[l + 1], K = M.width[l];
+        const float* __restrict__ W = M.w[l];
+        const int k0 = 32 * wave + col, k1 = k0 + 128;
+        const bool live0 = k0 < K, live1 = k1 < K;
+        const bool strip0 = 32 * wave < K && (l > 0 || 32 * wave + 32 > Dx), strip1 = 32 * wave + 128 < K && (l > 0 || 32 * wave + 160 > Dx);
+        const float* w0 = W + (live0 ? k0 : 0);
+        const float* w1 = W + (live1 ? k1 : 0);
+        MlpAcc acc0, acc1;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { acc0[reg] = 0.f; acc1[reg] = 0.f; }
+        if (strip0 && strip1) mlp_chain_t<2>(tile, w0, w1, J, K, lane, acc0, acc1);
+        else if (strip0) mlp_chain_t<1>(tile, w0, w1, J, K, lane, acc0, acc1);
+        else if (strip1) mlp_chain_t<1>(tile, w1, w0, J, K, lane, acc1, acc0);   /* layer 0 alone: strip `wave + 4` without strip `wave` */
+        __syncthreads();                                         /* every wavefront has read delta_l */
+        const unsigned int mask = l == 0 ? 0xffffffffu : (l == 1 ? m1 : (l == 2 ? m2 : m3));
+        float* __restrict__ out = l == 0 ? ga : nullptr;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int r = mlp_row(reg, lane);
+            const bool inb = row0 + r < M.B;
+            if (strip0) {
+                const float v = live0 && ((mask >> reg) & 1u) ? acc0[reg] : 0.f;
+                tile[r * MLP_LD + k0] = v;
+                if (out && live0 && k0 >= Dx && inb) out[(row0 + r) * gas + (k0 - Dx)] = v;
+            }
+            if (strip1) {
+                const float v = live1 && ((mask >> (16 + reg)) & 1u) ? acc1[reg] : 0.f;
+                tile[r * MLP_LD + k1] = v;
+                if (out && live1 && k1 >= Dx && inb) out[(row0 + r) * gas + (k1 - Dx)] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+/* P: the actor, Q: the critic, G: the actor's gradient arguments (x, out, grads, dw / db, the workspace; gx = ga = null, so mlp_backward
+ * stops in front of the actor's layer 0), X: what belongs to neither network */
+__global__ void __launch_bounds__(256, 2) pmg_k_policy_grad_rows(PmgMlp P, PmgMlp Q, PmgGrad G, PmgPolicy X)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L];
+    const MlpRawRows S = {G.x, G.xs};
+    float* __restrict__ stash = G.grads ? G.wd[P.L - 1] : nullptr;
+    const bool back = G.grads || X.ga, critic = back || X.q;
+    const int r = t >> 3;                                        /* the row of this thread in both hand-overs: 8 units of all 32 rows per pass */
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS, row = row0 + r;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        unsigned int am1 = 0, am2 = 0, am3 = 0, cm1 = 0, cm2 = 0, cm3 = 0;
+        mlp_layers_saved(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+        /* pmg_k_td_target's hand-over: z in columns [0, A) -> a = clip(o) in columns [Dx, Dx + A), the units in DESCENDING order.  The passes
+         * are cut at multiples of 8 from unit 0, as the hand-back's are: unit j of a row is the same thread's both times */
+        for (int lo = (A - 1) & ~7; lo >= 0; lo -= 8) {
+            const int j = lo + (t & 7);
+            const float z = j < A ? tile[r * MLP_LD + j] : 0.f;
+            __syncthreads();                                     /* the pass has read its z: columns [Dx + lo, Dx + lo + 8) are free */
+            if (j < A) {
+                const float o = P.out_act ? tanhf(z) : z, a = fminf(fmaxf(o, -1.f), 1.f);
+                tile[r * MLP_LD + Dx + j] = row < P.B ? a : 0.f;
+                if (row < P.B) {
+                    if (X.action) X.action[row * X.as + j] = a;
+                    if (G.out) G.out[row * G.os + j] = o;
+                    if (stash) stash[row * A + j] = o;
+                }
+            }
+        }
+        if (critic) {
+            mlp_gather(tile, S, row0, P.B, Dx, Dx, t);           /* columns below Dx: no pass wrote them, every pass is done reading */
+            if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+            __syncthreads();
+            mlp_layers_masked(tile, Q, lane, wave, col, cm1, cm2, cm3);
+            /* the critic's head in column 0; column 1, the padding of its single output, is +0.0 from the last layer's whole strip */
+            if (t < MLP_ROWS) {
+                float d = 0.f;
+                if (row0 + t < P.B) {
+                    const float z = tile[t * MLP_LD], q = Q.out_act ? tanhf(z) : z;
+                    if (X.q) X.q[row0 + t] = q;
+                    d = Q.out_act ? X.gscale * fmaf(-q, q, 1.f) : X.gscale;
+                }
+                tile[t * MLP_LD] = d;
+            }
+            __syncthreads();
+        }
+        if (back) mlp_backward_action(tile, Q, Dx, X.ga, X.gas, row0, lane, wave, col, cm1, cm2, cm3);
+        if (G.grads) {
+            /* the hand-back, the hand-over's mirror: ga in columns [Dx, Dx + A) -> the actor's delta_{L-1} in columns [0, A).  The values move DOWN,
+             * so the passes run in ASCENDING order: a pass writes only columns below every column a later pass reads.  Every column the actor's
+             * first transposed chain reads is written here for all 32 rows: rows past the batch and column A of an odd A as +0.0 */
+            for (int lo = 0; lo < A; lo += 8) {
+                const int j = lo + (t & 7);
+                const float ga = j < A ? tile[r * MLP_LD + Dx + j] : 0.f;
+                __syncthreads();                                 /* the pass has read its ga: columns [lo, lo + 8) are free */
+                if (j < A) {
+                    float d = 0.f;
+                    if (row < P.B) {
+                        const float o = stash[row * A + j];
+                        const float g = fmaf(X.l2scale, o, (o >= -1.f && o <= 1.f) ? ga : 0.f);
+                        d = P.out_act ? g * fmaf(-o, o, 1.f) : g;
+                        stash[row * A + j] = d;
+                    }
+                    tile[r * MLP_LD + j] = d;
+                }
+            }
+            if (A & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + A] = 0.f; }
+            __syncthreads();
+            mlp_backward(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+        }
+        __syncthreads();                                         /* the next tile's rows overwrite this one's */
+    }
+}
+hipError_t pmg_launch_policy_grad(const PmgMlp& P, const PmgMlp& Q, const PmgGrad& G, const PmgPolicy& X, const PmgGradChunks* C, const PmgSegs* T,
+                                  hipStream_t s)
+{
+    if (P.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pmg_k_policy_grad_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, Q, G, X);
+    if (G.grads) {
+        const MlpRawRows S = {G.x, G.xs};
+        if (!C) hipLaunchKernelGGL((pmg_k_mlp_grad_weights<MlpRawRows>), dim3(pmg_grad_w_tiles(P)), dim3(64), 0, s, S, P, G);
+        else {
+            hipLaunchKernelGGL((pmg_k_mlp_grad_partials<MlpRawRows>), dim3((unsigned)(C->C * C->tiles)), dim3(64), 0, s, S, P, G, *C);
+            hipLaunchKernelGGL(pmg_k_mlp_grad_merge, dim3(seg_grid(*T)), dim3(256), 0, s, *T, (const float*)C->part, C->C, C->P);
+        }
+    }
     return hipGetLastError();
 }
