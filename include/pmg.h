@@ -467,6 +467,52 @@ typedef struct pmg_policy_grad {
 int64_t pmg_policy_grad_work_floats(const pmg_mlp* actor, const pmg_mlp* critic, int64_t batch, int64_t chunk_rows);   /* chunk_rows 0: one chain; < 0: invalid */
 int pmg_policy_grad_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows);
 
+/* pmg_td3_target_device (normative), float32 throughout: the TD target of TD3 in one call -- target-policy smoothing and the
+ * smaller of two target critics,
+ *   y = clip(r + gamma * min(Q1'(x', a~), Q2'(x', a~))),   a~ = clip(clip(pi'(x')) + clip(sigma * n, -c, c), -1, 1),   n ~ N(0, 1).
+ * Stream-ordered on the handle's stream, syncs nothing, writes only its outputs and d_work, touches no state of the handle.  Per row b,
+ * Dx = actor.width[0], A = actor.width[L]:
+ *   1. z = the actor's layer chain on x'[b];  a0[j] = min(max(actor.out_activation ? tanhf(z[j]) : z[j], -1), 1), the a' of pmg_td_target_device.
+ *   2. sigma > 0: the draws are those of pmg_her_sample_device with s = (row_offset + b) * A + j as the sample index:
+ *      key = mix(seed ^ mix(counter + GOLD)), r_k = mix(key + (4 s + k + 1) GOLD) >> 32, u1 = ((r_0 >> 8) + 1) 2^-24, u2 = (r_1 >> 8) 2^-24
+ *      as pmg_act_env_device forms them (r_2 and r_3 are not used);
+ *        e    = fminf(fmaxf(sigma * sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2), -c), c)
+ *        a~[j] = fminf(fmaxf(a0[j] + e, -1.f), 1.f)
+ *      sigma == 0: no draw is made and a~ = a0 bit for bit.
+ *   3. q1 = critic1.out_activation(z_c1), z_c1 = critic 1's chain on the row x'[b] | a~; q2 likewise from critic 2; qmin = fminf(q1, q2): a
+ *      NaN loses against a number, and of two zeros of opposite sign either may be returned.  critic2 == NULL: qmin = q1.
+ *   4. t = terminal ? r : fmaf(gamma, qmin, r);  y = fminf(fmaxf(t, clip_lo), clip_hi)   (the sign of a zero y as for pmg_td_target_device).
+ * With critic2 == NULL and sigma == 0 the call returns the bits of pmg_td_target_device.  A row's outputs depend on its own x', r, terminal
+ * flag, the weights and (seed, counter, row_offset + b): not on the batch, the grid or the rows around it; two calls on the same inputs
+ * give the same bits.  A batch cut into pieces gives the same rows when each piece passes the index of its first row as row_offset.
+ * Workspace: pmg_td3_target_work_floats = batch * A floats when a second critic is given and d_next_action is NULL (a~ has to be kept for
+ * critic 2 somewhere), else 0 (d_work may then be NULL); < 0 for an invalid actor or batch.
+ * PMG_E_INVALID, with nothing launched: everything pmg_td_target_device rejects, for every given network; critic2 not shaped
+ * Dx + A -> ... -> 1 (its depth and hidden widths may differ from critic 1's); sigma negative or not finite; noise_clip negative or NaN
+ * (+inf: the noise is not clipped); row_offset < 0; a wrong struct_size; d_work NULL or work_floats too small where the figure above is
+ * positive; a float pointer off 4 bytes.  batch == 0 is a successful no-op. */
+typedef struct pmg_td3_target {
+    int32_t struct_size, reserved;
+    float gamma;                         /* finite, >= 0 */
+    float clip_lo, clip_hi;              /* as pmg_td_target */
+    float sigma;                         /* >= 0, finite; 0: no noise term at all, no draw is made */
+    float noise_clip;                    /* c >= 0, +inf allowed (no clip of the noise); NaN invalid */
+    uint64_t seed, counter;              /* the draws are a pure function of (seed, counter, row_offset + b, j) */
+    int64_t row_offset;                  /* >= 0: index of row 0 in the caller's numbering of samples */
+    int64_t batch;
+    const float* d_x_next; int64_t x_stride;   /* [B, Dx] at x_stride floats from row to row */
+    const float* d_reward;               /* [B] */
+    const uint8_t* d_terminal;           /* [B] or NULL; non-zero: no bootstrap term, t = r */
+    float* d_y;                          /* [B]     required */
+    float* d_q_min;                      /* [B]     or NULL: min(q1, q2) */
+    float* d_q1; float* d_q2;            /* [B]     or NULL each (d_q2 is not written without a second critic) */
+    float* d_next_action;                /* [B, A]  or NULL: a~, the smoothed action both critics saw */
+    float* d_work; int64_t work_floats;  /* scratch, at least pmg_td3_target_work_floats(actor_target, critic2 != NULL, d_next_action != NULL, batch) */
+} pmg_td3_target;
+int64_t pmg_td3_target_work_floats(const pmg_mlp* actor_target, int has_critic2, int has_next_action, int64_t batch);
+int pmg_td3_target_device(pmg_env* env, const pmg_mlp* actor_target, const pmg_mlp* critic1_target,
+                          const pmg_mlp* critic2_target /* NULL: one critic */, const pmg_td3_target* td);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

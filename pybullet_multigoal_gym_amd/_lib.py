@@ -66,6 +66,14 @@ class PmgTdTarget(C.Structure):
                 ('d_y', C.c_void_p), ('d_q_next', C.c_void_p), ('d_next_action', C.c_void_p)]
 
 
+class PmgTd3Target(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gamma', C.c_float), ('clip_lo', C.c_float), ('clip_hi', C.c_float),
+                ('sigma', C.c_float), ('noise_clip', C.c_float), ('seed', C.c_uint64), ('counter', C.c_uint64), ('row_offset', C.c_int64),
+                ('batch', C.c_int64), ('d_x_next', C.c_void_p), ('x_stride', C.c_int64), ('d_reward', C.c_void_p), ('d_terminal', C.c_void_p),
+                ('d_y', C.c_void_p), ('d_q_min', C.c_void_p), ('d_q1', C.c_void_p), ('d_q2', C.c_void_p), ('d_next_action', C.c_void_p),
+                ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
+
+
 class PmgMlpParams(C.Structure):
     _fields_ = [('d_weight', C.c_void_p * 4), ('d_bias', C.c_void_p * 4)]
 
@@ -111,7 +119,8 @@ class PmgLibrary:
                'pmg_norm_write', 'pmg_policy_input_device', 'pmg_policy_input', 'pmg_policy_input_env_device',
                'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
                'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
-               'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device']
+               'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device',
+               'pmg_td3_target_work_floats', 'pmg_td3_target_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -135,6 +144,7 @@ class PmgLibrary:
         L.pmg_mlp_grad_work_floats.restype = C.c_int64
         L.pmg_mlp_grad_chunked_work_floats.restype = C.c_int64
         L.pmg_policy_grad_work_floats.restype = C.c_int64
+        L.pmg_td3_target_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -382,6 +392,23 @@ class PmgHandle:
     def td_target_device(self, actor_target, critic_target, td):
         """y = clip(r + gamma Q'(x', pi'(x'))) of a td_struct(); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_td_target_device(self.h, C.byref(actor_target), C.byref(critic_target), C.byref(td)))
+
+    # -- TD3's target: twin critics and target-policy smoothing (include/pmg.h, DESIGN.md 3.14) --
+    @staticmethod
+    def td3_struct(batch, d_x_next, x_stride, d_reward, d_y, gamma, clip_lo=-float('inf'), clip_hi=float('inf'), sigma=0.0, noise_clip=float('inf'),
+                   seed=0, counter=0, row_offset=0, d_terminal=None, d_q_min=None, d_q1=None, d_q2=None, d_next_action=None, d_work=None, work_floats=0):
+        """pmg_td3_target from device pointers (integers or None)."""
+        return PmgTd3Target(C.sizeof(PmgTd3Target), 0, gamma, clip_lo, clip_hi, sigma, noise_clip, seed & (2 ** 64 - 1), counter & (2 ** 64 - 1),
+                            row_offset, batch, d_x_next, x_stride, d_reward, d_terminal, d_y, d_q_min, d_q1, d_q2, d_next_action, d_work, work_floats)
+
+    def td3_target_work_floats(self, actor_target, has_critic2, has_next_action, batch):
+        """floats of workspace pmg_td3_target_device needs: batch * A with a second critic and no d_next_action, else 0 (< 0: invalid)"""
+        return int(self.L.lib.pmg_td3_target_work_floats(C.byref(actor_target), C.c_int(bool(has_critic2)), C.c_int(bool(has_next_action)), C.c_int64(batch)))
+
+    def td3_target_device(self, actor_target, critic1_target, critic2_target, td):
+        """y = clip(r + gamma min(Q1', Q2')(x', smoothed pi'(x'))) of a td3_struct(); critic2_target may be None; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_td3_target_device(self.h, C.byref(actor_target), C.byref(critic1_target),
+                                                     C.byref(critic2_target) if critic2_target is not None else None, C.byref(td)))
 
     # -- back-propagation, Adam, Polyak (include/pmg.h, DESIGN.md 3.11) --
     @staticmethod

@@ -23,6 +23,26 @@ The actor's line is the whole actor loss of HER, ``-mean Q(x, clip(pi(x))) + act
 call differentiates ``gscale * sum Q + l2scale / 2 * sum pi^2``, so ``gscale = -1 / B`` carries the mean over the batch and
 ``l2scale = 2 * action_l2 / (B * A)`` the mean over the B * A outputs and the 2 of the square's derivative; ``l2scale = 0`` is plain DDPG.
 The gradient is zero where the clip is active, and the L2 term acts on the unclipped output.
+
+TD3 is the same sequence with two critics and ``td3_target_device`` in place of ``td_target_device``: one target call with
+target-policy smoothing and the smaller of the two target critics, the two critics' gradients on the SAME ``d_y``, and the actor and the
+three Polyak updates on every ``policy_delay``-th update only -- a host-side ``if`` (``critic2, critic2_t = Critic(env), Critic(env)``, loaded;
+``u`` counts the updates):
+
+    s2 = critic2.adam_state()
+    critic_t.td3_target_device(actor_t, critic2_t, d_xn, d_r, d_y, 0.98, -1 / (1 - 0.98), 0.0, 0.2, 0.5, seed, u,      # sigma 0.2, noise_clip 0.5
+                               d_terminal=d_ok, d_next_action=d_na, batch=B)                                            # y; counter = u: fresh noise
+    for c, s in ((critic, sc), (critic2, s2)):
+        c.grad_device(B, d_x, Dx, d_work, work, d_a=d_a, a_dim=A, d_target=d_y, gscale=2.0 / B, grads=s.g, chunk_rows=R)
+        c.adam_step_device(s.g, s, lr)
+    if u % policy_delay == 0:
+        actor.policy_grad_device(critic, B, d_x, d_work, work, gscale=-1.0 / B, l2scale=2.0 * action_l2 / (B * A), grads=sa.g, chunk_rows=R)
+        actor.adam_step_device(sa.g, sa, lr)
+        actor_t.soft_update_from(actor, tau); critic_t.soft_update_from(critic, tau); critic2_t.soft_update_from(critic2, tau)
+
+The smoothed action both target critics saw goes to ``d_next_action`` [B, A]; without it the call keeps it in ``d_work``
+(``td3_target_work_floats`` floats).  The noise of row b is a function of ``(seed, counter, row_offset + b)``, so a batch cut into pieces
+(``row_offset`` = the piece's first row) gives the rows of the whole.  ``critic2 = None, sigma = 0`` is ``td_target_device``, bit for bit.
 """
 import numpy as np
 
@@ -142,6 +162,88 @@ class Critic(Trainable):
             for p in ptrs:
                 h.device_free(p)
         return y, qn, na
+
+    def _twin(self, critic2):
+        if critic2 is None:
+            return None
+        if not isinstance(critic2, Critic):
+            raise ValueError('critic2 must be a Critic (whose loaded network is the second target critic) or None, not %r' % (type(critic2),))
+        mlp2 = critic2._loaded()
+        if critic2.widths[0] != self.widths[0]:
+            raise ValueError('critic2 takes %d inputs, this critic %d' % (critic2.widths[0], self.widths[0]))
+        return mlp2
+
+    def td3_target_work_floats(self, actor, critic2, batch, next_action=False):
+        """floats of workspace ``td3_target_device`` needs: batch * A with a second critic and no d_next_action, else 0."""
+        self._loaded()
+        return self._h.td3_target_work_floats(self._target_actor(actor), critic2 is not None, next_action, int(batch))
+
+    def td3_target_device(self, actor, critic2, d_x_next, d_reward, d_y, gamma, clip_lo, clip_hi, sigma, noise_clip, seed, counter, row_offset=0,
+                          d_terminal=None, d_q_min=None, d_q1=None, d_q2=None, d_next_action=None, d_work=None, work_floats=0, x_stride=None, *, batch):
+        """TD3's target in one call: d_y [batch] = clip(r + gamma min(Q1', Q2')(x', a~)), a~ = clip(clip(pi'(x')) + clip(sigma n, -noise_clip,
+        noise_clip), -1, 1), with this network as Q1', ``critic2``'s as Q2' (None: one critic, min = Q1') and ``actor``'s as pi'.  The draws n
+        are a function of (seed, counter, row_offset + row, column); sigma = 0: no noise, no draw.  d_terminal, d_q_min, d_q1, d_q2 [batch] and
+        d_next_action [batch, A] (a~) are optional.  With a second critic and without d_next_action, d_work holds at least
+        ``td3_target_work_floats`` floats.  Allocates nothing; on the handle's stream, no host sync."""
+        mlp = self._loaded()
+        amlp = self._target_actor(actor)
+        mlp2 = self._twin(critic2)
+        gamma, clip_lo, clip_hi, sigma, noise_clip = float(gamma), float(clip_lo), float(clip_hi), float(sigma), float(noise_clip)
+        if not gamma >= 0.0 or not np.isfinite(gamma):
+            raise ValueError('gamma %r must be finite and >= 0' % (gamma,))
+        if not clip_lo <= clip_hi:
+            raise ValueError('clips %r / %r must be ordered and not NaN' % (clip_lo, clip_hi))
+        if not sigma >= 0.0 or not np.isfinite(sigma):
+            raise ValueError('sigma %r must be finite and >= 0' % (sigma,))
+        if not noise_clip >= 0.0:
+            raise ValueError('noise_clip %r must be >= 0 and not NaN' % (noise_clip,))
+        if int(row_offset) < 0:
+            raise ValueError('row_offset %r must be >= 0' % (row_offset,))
+        h = self._h
+        td = h.td3_struct(int(batch), d_x_next, actor.widths[0] if x_stride is None else x_stride, d_reward, d_y, gamma, clip_lo, clip_hi, sigma,
+                          noise_clip, int(seed), int(counter), int(row_offset), d_terminal, d_q_min, d_q1, d_q2, d_next_action, d_work, int(work_floats))
+        h.td3_target_device(amlp, mlp, mlp2, td)
+
+    def td3_target(self, actor, critic2, x_next, reward, gamma, clip_lo=-float('inf'), clip_hi=float('inf'), sigma=0.0, noise_clip=float('inf'),
+                   seed=0, counter=0, row_offset=0, terminal=None):
+        """x_next [B, Dx], reward [B], terminal [B] or None -> y [B], q_min [B], q1 [B], q2 [B] (None without critic2), next_action [B, A]
+        (numpy)."""
+        self._loaded()
+        self._target_actor(actor)
+        self._twin(critic2)
+        h = self._h
+        Dx, A = actor.widths[0], actor.widths[-1]
+        x_next, reward = np.ascontiguousarray(x_next, np.float32), np.ascontiguousarray(reward, np.float32)
+        if x_next.ndim != 2 or x_next.shape[1] != Dx or reward.shape != (x_next.shape[0],):
+            raise ValueError('x_next %s must be [B, %d] and reward %s [B]' % (x_next.shape, Dx, reward.shape))
+        B = x_next.shape[0]
+        if terminal is not None:
+            terminal = np.ascontiguousarray(np.asarray(terminal) != 0, np.uint8)
+            if terminal.shape != (B,):
+                raise ValueError('terminal %s must be [B]' % (terminal.shape,))
+        y, qm, q1, na = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32), np.empty((B, A), np.float32)
+        q2 = np.empty(B, np.float32) if critic2 is not None else None
+        if B == 0:
+            return y, qm, q1, q2, na
+        ins = [x_next, reward] + ([terminal] if terminal is not None else [])
+        outs = [y, qm, q1, na] + ([q2] if q2 is not None else [])
+        ptrs = []
+        try:
+            for arr in ins + outs:
+                ptrs.append(h.device_alloc(arr.nbytes))
+            for p, arr in zip(ptrs, ins):
+                h.upload(p, arr)
+            d_out = ptrs[len(ins):]
+            self.td3_target_device(actor, critic2, ptrs[0], ptrs[1], d_out[0], gamma, clip_lo, clip_hi, sigma, noise_clip, seed, counter, row_offset,
+                                   d_terminal=ptrs[2] if terminal is not None else None, d_q_min=d_out[1], d_q1=d_out[2],
+                                   d_q2=d_out[4] if q2 is not None else None, d_next_action=d_out[3], batch=B)
+            h.sync()
+            for arr, p in zip(outs, d_out):
+                h.download(arr, p)
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+        return y, qm, q1, q2, na
 
     def close(self):
         """Free the uploaded network and the Adam states made for it."""

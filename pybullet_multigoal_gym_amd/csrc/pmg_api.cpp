@@ -1075,6 +1075,65 @@ int pmg_td_target_device(pmg_env* e, const pmg_mlp* actor_target, const pmg_mlp*
     return PMG_OK;
 }
 
+/* ---- TD3's target: twin critics, target-policy smoothing ---- */
+int64_t pmg_td3_target_work_floats(const pmg_mlp* actor_target, int has_critic2, int has_next_action, int64_t batch)
+{
+    if (!actor_target || actor_target->struct_size != (int32_t)sizeof(pmg_mlp) || actor_target->num_layers < 1 || actor_target->num_layers > 4) return -1;
+    if (batch < 0 || batch > ((int64_t)1 << 40)) return -1;
+    const int A = actor_target->width[actor_target->num_layers];
+    if (A < 1 || A > 256) return -1;
+    return has_critic2 && !has_next_action ? batch * A : 0;
+}
+
+int pmg_td3_target_device(pmg_env* e, const pmg_mlp* actor_target, const pmg_mlp* critic1_target, const pmg_mlp* critic2_target, const pmg_td3_target* td)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_td3_target_device";
+    PmgMlp P, Q1, Q2;
+    if (int rc = mlp_of(e, actor_target, "pmg_td3_target_device (actor)", P)) return rc;
+    if (int rc = mlp_of(e, critic1_target, "pmg_td3_target_device (critic 1)", Q1)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L];
+    if (int rc = critic_of(e, Q1, Dx + A, "pmg_td3_target_device (critic 1)")) return rc;
+    if (critic2_target) {
+        if (int rc = mlp_of(e, critic2_target, "pmg_td3_target_device (critic 2)", Q2)) return rc;
+        if (int rc = critic_of(e, Q2, Dx + A, "pmg_td3_target_device (critic 2)")) return rc;
+    } else
+        Q2 = Q1;
+    if (!td) return fail(e, PMG_E_INVALID, "%s: td is null", who);
+    if (td->struct_size != (int32_t)sizeof(pmg_td3_target)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, td->struct_size, sizeof(pmg_td3_target));
+    if (!td->d_x_next || !td->d_reward || !td->d_y) return fail(e, PMG_E_INVALID, "%s: d_x_next, d_reward or d_y is null", who);
+    if ((((size_t)td->d_x_next | (size_t)td->d_reward | (size_t)td->d_y | (size_t)td->d_q_min | (size_t)td->d_q1 | (size_t)td->d_q2 | (size_t)td->d_next_action |
+          (size_t)td->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (td->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)td->batch);
+    if (td->x_stride < Dx) return fail(e, PMG_E_INVALID, "%s: x_stride %lld is smaller than the width %d", who, (long long)td->x_stride, Dx);
+    if (!(td->gamma >= 0.f) || std::isinf(td->gamma)) return fail(e, PMG_E_INVALID, "%s: gamma %g must be finite and >= 0", who, (double)td->gamma);
+    if (!(td->clip_lo <= td->clip_hi)) return fail(e, PMG_E_INVALID, "%s: clips %g / %g must be ordered and not NaN", who, (double)td->clip_lo, (double)td->clip_hi);
+    if (!(td->sigma >= 0.f) || std::isinf(td->sigma)) return fail(e, PMG_E_INVALID, "%s: sigma %g must be finite and >= 0", who, (double)td->sigma);
+    if (!(td->noise_clip >= 0.f)) return fail(e, PMG_E_INVALID, "%s: noise_clip %g must be >= 0 and not NaN", who, (double)td->noise_clip);
+    if (td->row_offset < 0) return fail(e, PMG_E_INVALID, "%s: row_offset %lld is negative", who, (long long)td->row_offset);
+    const int64_t need = pmg_td3_target_work_floats(actor_target, critic2_target != nullptr, td->d_next_action != nullptr, td->batch);
+    if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)td->batch);
+    if (need > 0 && (!td->d_work || td->work_floats < need))
+        return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld is below the %lld floats the smoothed action of critic 2 needs", who,
+                    (long long)td->work_floats, (long long)need);
+    if (td->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = Q1.B = Q2.B = td->batch;
+    PmgTd3 X;
+    memset(&X, 0, sizeof(X));
+    X.T.xn = td->d_x_next; X.T.xs = td->x_stride; X.T.reward = td->d_reward; X.T.term = td->d_terminal;
+    X.T.gamma = td->gamma; X.T.lo = td->clip_lo; X.T.hi = td->clip_hi;
+    X.T.y = td->d_y; X.T.qn = td->d_q_min;
+    X.q1 = td->d_q1; X.q2 = critic2_target ? td->d_q2 : nullptr;
+    X.twin = critic2_target != nullptr;
+    X.keep = td->d_next_action ? td->d_next_action : (X.twin ? td->d_work : nullptr);
+    X.noise = td->sigma > 0.f; X.sigma = td->sigma; X.c = td->noise_clip;
+    X.seed = td->seed; X.counter = td->counter; X.row_offset = (unsigned long long)td->row_offset;
+    HIP_TRY(e, pmg_launch_td3_target(P, Q1, Q2, X, e->stream));
+    return PMG_OK;
+}
+
 /* ---- back-propagation, Adam, Polyak ---- */
 int64_t pmg_mlp_grad_work_floats(const pmg_mlp* mlp, int64_t batch)
 {

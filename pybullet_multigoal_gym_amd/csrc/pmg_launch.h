@@ -81,6 +81,19 @@ struct PmgTd {
 };
 hipError_t pmg_launch_mlp_q(const PmgMlp& M, const float* d_x, long long x_stride, int x_dim, const float* d_a, long long a_stride, hipStream_t s);
 hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const PmgTd& T, hipStream_t s);
+/* TD3's target (pmg_td3_target_device), validated by the caller.  T as for pmg_launch_td_target with qn = q_min; T.na is not
+ * used: keep = where the smoothed action a~ [B, A] (contiguous) is written and, with a second critic, read back -- the caller's
+ * d_next_action when given, else the workspace when twin, else null.  q1 / q2 may be null.  noise != 0: sigma > 0, draws from (seed, counter),
+ * sample index (row_offset + row) * A + j; c = the clip of the noise (may be +inf).  critic2 is read only when twin != 0. */
+struct PmgTd3 {
+    PmgTd T;
+    float* q1; float* q2; float* keep;
+    int twin, noise;
+    float sigma, c;
+    unsigned long long seed, counter, row_offset;
+    unsigned long long key;                             /* mix(seed ^ mix(counter + GOLD)): set by the launcher */
+};
+hipError_t pmg_launch_td3_target(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgTd3& X, hipStream_t s);
 
 /* back-propagation, Adam and Polyak (pmg_mlp_grad_device, pmg_mlp_adam_device, pmg_mlp_polyak_device), validated by the caller.
  * Rows x[r] | a[r] as pmg_launch_mlp_q takes them (a == null: raw rows of x_dim = width[0] floats).  dw / db: the gradient tensors, used iff

@@ -673,6 +673,88 @@ __global__ void __launch_bounds__(256) pmg_k_td_target(PmgMlp P, PmgMlp Q, PmgTd
         __syncthreads();                                             /* the next tile's rows overwrite this one's */
     }
 }
+/* TD3's target (pmg_td3_target_device, DESIGN.md 3.14), pmg_k_td_target's sibling on the same tile: y = clip(r + gamma min(Q1', Q2')(x', a~)),
+ * a~ = clip(a' + clip(sigma n, -c, c), -1, 1).  The actor, the descending hand-over, the regather of x' and critic 1 run as there; the noise is
+ * added inside the hand-over pass by the thread that owns (row, unit), which also writes a~ to X.keep (the caller's d_next_action, or the
+ * workspace).  Critic 1's layers overwrite the whole tile, so for critic 2 the row x' | a~ is built again: x' from memory, a~ from X.keep by
+ * the SAME (row, unit) -> thread map as the hand-over -- a thread reads only its own earlier store, so no ordering between threads is
+ * involved (the argument of pmg_k_policy_grad_rows for its stash of o).  q1 waits in a register of the row's thread (t < 32) meanwhile.
+ * Stale tile between the critics: when the restore starts, the tile holds critic 1's activations (which may be inf) in columns up to its
+ * widest layer.  The regather writes columns [0, Dx) of all 32 rows, the restore passes columns [Dx, Dx + A) of all 32 rows, thread t < 32
+ * column Dx + A of an odd Dx + A; rows past the batch receive +0.0 in each.  These are all the columns critic 2's layer 0 reads (K = Dx + A,
+ * and the padding column of an odd K), so no stale activation meets a weight or a stand-in zero.  Nothing in the restore READS the tile,
+ * so its passes need no barrier between them; the barrier in front of it orders the read of q1 (column 0) before the regather's writes. */
+/* the smoothing term e of sample index s = (row_offset + row) * A + j: mlp_action's expression with sigma for noise_eps, clipped to [-c, c] */
+__device__ __forceinline__ float td3_noise(const PmgTd3& X, unsigned long long s)
+{
+    const unsigned long long zb = X.key + (4ull * s + 1ull) * HER_GOLD;
+    const unsigned int r0 = (unsigned int)(her_mix(zb) >> 32), r1 = (unsigned int)(her_mix(zb + HER_GOLD) >> 32);
+    const float u1 = (float)((r0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r1 >> 8) * 0x1p-24f;
+    return fminf(fmaxf(X.sigma * sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2), -X.c), X.c);
+}
+__global__ void __launch_bounds__(256) pmg_k_td3_target(PmgMlp P, PmgMlp Q1, PmgMlp Q2, PmgTd3 X)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L];
+    const MlpRawRows S = {X.T.xn, X.T.xs};
+    const int r = t >> 3;                                            /* the row of this thread in the hand-over and in the restore */
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS, row = row0 + r;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        mlp_layers(tile, P, lane, wave, col);
+        for (int hi = A; hi > 0; hi -= 8) {
+            const int j = hi - 8 + (t & 7);                          /* units [hi - 8, hi) of the 32 rows */
+            const float z = j >= 0 ? tile[r * MLP_LD + j] : 0.f;
+            __syncthreads();                                         /* the pass has read its z: columns [Dx + hi - 8, Dx + hi) are free */
+            if (j >= 0) {
+                float a = 0.f;
+                if (row < P.B) {
+                    a = mlp_plain_action(P.out_act, z);
+                    if (X.noise) a = fminf(fmaxf(a + td3_noise(X, (X.row_offset + (unsigned long long)row) * (unsigned long long)A + (unsigned long long)j), -1.f), 1.f);
+                    if (X.keep) X.keep[row * A + j] = a;
+                }
+                tile[r * MLP_LD + Dx + j] = a;
+            }
+        }
+        mlp_gather(tile, S, row0, P.B, Dx, Dx, t);                   /* columns below Dx: no pass wrote them, every pass is done reading */
+        if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+        __syncthreads();
+        mlp_layers(tile, Q1, lane, wave, col);
+        const bool own = t < MLP_ROWS && row0 + t < P.B;             /* this thread forms the outputs of row row0 + t */
+        float q = 0.f;
+        if (own) {
+            const float z = tile[t * MLP_LD];
+            q = Q1.out_act ? tanhf(z) : z;
+            if (X.q1) X.q1[row0 + t] = q;
+        }
+        if (X.twin) {
+            __syncthreads();                                         /* q1 is read: column 0 is free */
+            mlp_gather(tile, S, row0, P.B, Dx, Dx, t);
+            for (int hi = A; hi > 0; hi -= 8) {                      /* the hand-over's map: a thread reads what it stored itself */
+                const int j = hi - 8 + (t & 7);
+                if (j >= 0) tile[r * MLP_LD + Dx + j] = row < P.B ? X.keep[row * A + j] : 0.f;
+            }
+            if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+            __syncthreads();
+            mlp_layers(tile, Q2, lane, wave, col);
+            if (own) {
+                const float z = tile[t * MLP_LD], q2 = Q2.out_act ? tanhf(z) : z;
+                if (X.q2) X.q2[row0 + t] = q2;
+                q = fminf(q, q2);
+            }
+        }
+        if (own) {
+            const float rw = X.T.reward[row0 + t];
+            const float v = X.T.term && X.T.term[row0 + t] ? rw : fmaf(X.T.gamma, q, rw);
+            X.T.y[row0 + t] = fminf(fmaxf(v, X.T.lo), X.T.hi);
+            if (X.T.qn) X.T.qn[row0 + t] = q;
+        }
+        __syncthreads();                                             /* the next tile's rows overwrite this one's */
+    }
+}
 static unsigned mlp_grid(long long B)
 {
     const long long want = (B + MLP_ROWS - 1) / MLP_ROWS;
@@ -705,6 +787,14 @@ hipError_t pmg_launch_td_target(const PmgMlp& actor, const PmgMlp& critic, const
 {
     if (actor.B <= 0) return hipSuccess;
     hipLaunchKernelGGL(pmg_k_td_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic, T);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_td3_target(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgTd3& T, hipStream_t s)
+{
+    if (actor.B <= 0) return hipSuccess;
+    PmgTd3 X = T;
+    X.key = her_mix(X.seed ^ her_mix(X.counter + HER_GOLD));
+    hipLaunchKernelGGL(pmg_k_td3_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic1, critic2, X);
     return hipGetLastError();
 }
 
