@@ -9,7 +9,7 @@
  * (the plain C++ branches of the same header), same symbols, two libraries. */
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include "pmg_contact.h"
+#include "pmg_kernels.h"   /* (pmg_contact.h, and the step bodies for the reach row set-up) */
 
 #define WV wv
 #define PRIM_FN prim_probe_wv
@@ -73,6 +73,21 @@ __global__ void __launch_bounds__(192) k_prim(int fam, int wave, int rowsel, int
             if (WR) prim_probe_wr(fam, src, in, out);
             else prim_probe_wv(fam, src, in, out);
         }
+}
+
+/* ---- the matrix-pipe primitive: one wavefront, every lane alive (prim::mfma_chain) ------------------------------------- */
+__global__ void __launch_bounds__(64) k_mfma(int n, int steps, const float* a, const float* b, const float* c, float* out)
+{
+    prim::mfma_chain(n, steps, a, b, c, out);
+}
+
+/* ---- the reach row set-up: one wavefront, the product's contact store (prim::rowsetup_cases) ----------------------------- */
+__global__ void __launch_bounds__(64) k_rowsetup(int n, const float* q, const float* qd, const float* con, const float* mu, const int* ncs, float* coef, float* resp,
+                                                 float* misc, float* S_out, float* minv_out)
+{
+    __shared__ pmg::ContactLds<0, 8> L;
+    __shared__ pmg::LaneTabStore lcs;
+    prim::rowsetup_cases(L, lcs, n, q, qd, con, mu, ncs, coef, resp, misc, S_out, minv_out);
 }
 
 /* ---- dynamics / IK: the bodies of pmge_probe_dynamics / pmge_probe_ik (tests/emu/pmg_probe.cpp), case after case ---- */
@@ -299,6 +314,37 @@ int pmgd_prim(int wr_ns, int fam, int threads, int wave, int rowsel, int src, co
     d.down(out, dout, (size_t)prim::NOUT * 64);
     return (int)d.err;
 }
+
+/* wv::mfma_32x32x2, `steps` (1..8) chained calls per case: a, b [n][steps][64], c [n][16][64] -> out [n][16][64] */
+int pmgd_mfma(int n, int steps, const float* a, const float* b, const float* c, float* out)
+{
+    if (n < 1 || n > prim::MFMA_MAX_CASES || steps < 1 || steps > prim::MFMA_MAX_STEPS) return -1;
+    Dev d;
+    const float *da = d.up(a, (size_t)n * steps * 64), *db = d.up(b, (size_t)n * steps * 64), *dc = d.up(c, (size_t)n * 16 * 64);
+    float* dout = d.up<float>(nullptr, (size_t)n * 16 * 64);
+    if (d.err == hipSuccess) hipLaunchKernelGGL(k_mfma, dim3(1), dim3(64), 0, 0, n, steps, da, db, dc, dout);
+    d.sync();
+    d.down(out, dout, (size_t)n * 16 * 64);
+    return (int)d.err;
+}
+
+/* pmg::reach_rowspace_setup<0, 8> on n (1..64) cases: prim::rowsetup_cases for the arguments */
+int pmgd_rowsetup(int n, const float* q, const float* qd, const float* con, const float* mu, const int* ncs, float* coef, float* resp, float* misc, float* S_out,
+                  float* minv_out)
+{
+    if (n < 1 || n > prim::ROWSETUP_MAX_CASES) return -1;
+    Dev d;
+    const float *dq = d.up(q, 9 * (size_t)n), *dqd = d.up(qd, 9 * (size_t)n), *dcon = d.up(con, 96 * (size_t)n), *dmu = d.up(mu, 8 * (size_t)n);
+    const int* dn = d.up(ncs, (size_t)n);
+    float *dc = d.up<float>(nullptr, 64 * 24 * (size_t)n), *dr = d.up<float>(nullptr, 64 * 9 * (size_t)n), *dm = d.up<float>(nullptr, 64 * 4 * (size_t)n);
+    float *dS = d.up<float>(nullptr, 54 * (size_t)n), *dmi = d.up<float>(nullptr, 81 * (size_t)n);
+    if (d.err == hipSuccess) hipLaunchKernelGGL(k_rowsetup, dim3(1), dim3(64), 0, 0, n, dq, dqd, dcon, dmu, dn, dc, dr, dm, dS, dmi);
+    d.sync();
+    d.down(coef, dc, 64 * 24 * (size_t)n); d.down(resp, dr, 64 * 9 * (size_t)n); d.down(misc, dm, 64 * 4 * (size_t)n);
+    d.down(S_out, dS, 54 * (size_t)n); d.down(minv_out, dmi, 81 * (size_t)n);
+    return (int)d.err;
+}
+int pmgd_rowspace_mfma() { return PMG_ROWSPACE_MFMA; }
 
 /* n cases: q, qd, tau [n][9] -> qdd [n][9], minv [n][81], tip [n][12] (position, rotation of the tip frame) */
 int pmgd_dynamics(int packed, int n, const float* q, const float* qd, const float* tau, float* qdd, float* minv_out, float* tip_out)

@@ -24,7 +24,96 @@ __device__ __forceinline__ void static_for(F&& f)
         static_for<I + 1, N>(f);
     }
 }
+/* The matrix-pipe primitive wv::mfma_32x32x2 (the shipped header's own definition in BOTH builds: its device form here, its
+ * PMG_EMULATE branch in the emulator), a chain of `steps` calls on one accumulator, all 64 lanes alive:
+ * a, b [n][steps][64], c [n][16][64] -> out [n][16][64], the last index the lane.  tests/mfma_cases.py */
+constexpr int MFMA_MAX_STEPS = 8, MFMA_MAX_CASES = 64;
+__device__ inline void mfma_chain(int n, int steps, const float* a, const float* b, const float* c, float* out)
+{
+    const int ln = (int)threadIdx.x & 63;
+    for (int i = 0; i < n; i++) {
+        wv::acc16 acc = wv::acc16_zero();
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = c[(16 * i + r) * 64 + ln];
+        for (int s = 0; s < steps; s++) acc = wv::mfma_32x32x2(a[(i * steps + s) * 64 + ln], b[(i * steps + s) * 64 + ln], acc);
+#pragma unroll
+        for (int r = 0; r < 16; r++) out[(16 * i + r) * 64 + ln] = acc[r];
+    }
+}
+/* The reach row set-up, pmg::reach_rowspace_setup<0, 8> (csrc/pmg_step_body.inc), for n cases one after the other on one wavefront.
+ * The lane state is built the way substep() builds it -- forward kinematics, joint subspaces published in the contact store, M^-1 --
+ * and the contact list is the caller's: q, qd [n][9]; con [n][8][12] (a b pa3 pb3 n3 dist), mu [n][8], ncs [n] (0..8)
+ * -> coef [n][64][24] (a lane's coefficient per source row), resp [n][64][9] (M^-1 J^T), misc [n][64][4] (den, rhs, dinv, mu), and the
+ * float32 operands the set-up worked from: S [n][9][6] (joint subspaces), minv [n][9][9].  tests/rowsetup_cases.py */
+constexpr int ROWSETUP_MAX_CASES = 64;
+__device__ inline void rowsetup_cases(pmg::ContactLds<0, 8>& L, pmg::LaneTabStore& lcs, int n, const float* q, const float* qd, const float* con, const float* mu,
+                                      const int* ncs, float* coef, float* resp, float* misc, float* S_out, float* minv_out)
+{
+    using namespace pmg;
+    LaneConst c;
+    load_lane_const(lcs, c);
+    const int l = wv::lane();
+    for (int i = 0; i < n; i++) {
+        const float ql = l < NJ ? q[9 * i + l] : 0.f, qdl = l < NJ ? qd[9 * i + l] : 0.f;
+        Kin k;
+        fk(c, ql, k);
+        publish_subspaces<0, 8>(L, k);
+        float I10[10], minv[NJ];
+        body_inertia(c, k, I10);
+        if (l >= NJ)
+            for (int a = 0; a < 10; a++) I10[a] = 0.f;
+        mass_inverse(k, I10, minv);
+        int nc = ncs[i];
+        nc = nc < 0 ? 0 : (nc > 8 ? 8 : nc);
+        if (l < 8) {
+            for (int a = 0; a < 12; a++) L.con[l][a] = l < nc ? con[(8 * i + l) * 12 + a] : 0.f;
+            L.con_mu[l] = l < nc ? mu[8 * i + l] : 0.f;
+        }
+        wv::lds_sync();
+        NcRows r;
+        r.dinv = r.den = r.rhs_m = r.rhs_l = r.imp_m = r.app_m = r.app_l = r.prev_m = r.prev_l = 0.f;
+        r.sg_l = 1.f; r.mot_active = 0x1FFu; r.lim_active = 0u;
+        McState mc;
+        for (int j = 0; j < NJ; j++) mc.A[j] = mc.sgnw[j] = 0.f;
+        mc.hi_l = 0.f; mc.lim_any = 0u; mc.fast = true;
+        ReachRowSet<24> w;
+        reach_rowspace_setup<0, 8>(L, nc, r, mc, minv, qdl, 0.f, w);
+        float* o = coef + (size_t)(64 * i + l) * 24;
+#pragma unroll
+        for (int s = 0; s < 24; s++) o[s] = w.c24[s];
+        o = resp + (size_t)(64 * i + l) * 9;
+#pragma unroll
+        for (int d = 0; d < NJ; d++) o[d] = w.Rm[d];
+        o = misc + (size_t)(64 * i + l) * 4;
+        o[0] = w.den; o[1] = w.rhs; o[2] = w.dinv; o[3] = w.mu;
+        if (l < NJ) {
+            for (int a = 0; a < 6; a++) S_out[(9 * i + l) * 6 + a] = k.S[a];
+            for (int j = 0; j < NJ; j++) minv_out[(9 * i + l) * 9 + j] = minv[j];
+        }
+        wv::lds_sync();
+    }
+}
 }  // namespace prim
+#ifdef PMG_EMULATE
+extern "C" int pmge_rowsetup(int n, const float* q, const float* qd, const float* con, const float* mu, const int* ncs, float* coef, float* resp, float* misc,
+                             float* S_out, float* minv_out)
+{
+    if (n < 1 || n > prim::ROWSETUP_MAX_CASES) return -1;
+    emu::launch(1, 64, [&]() {
+        __shared__ pmg::ContactLds<0, 8> L;
+        __shared__ pmg::LaneTabStore lcs;
+        prim::rowsetup_cases(L, lcs, n, q, qd, con, mu, ncs, coef, resp, misc, S_out, minv_out);
+    });
+    return 0;
+}
+extern "C" int pmge_rowspace_mfma() { return PMG_ROWSPACE_MFMA; }
+extern "C" int pmge_mfma(int n, int steps, const float* a, const float* b, const float* c, float* out)
+{
+    if (n < 1 || n > prim::MFMA_MAX_CASES || steps < 1 || steps > prim::MFMA_MAX_STEPS) return -1;
+    emu::launch(1, 64, [&]() { prim::mfma_chain(n, steps, a, b, c, out); });
+    return 0;
+}
+#endif
 #endif
 
 __device__ inline void PRIM_FN(int fam, int src, const float* in, float* out)

@@ -27,6 +27,7 @@
 #define PMG_DEVICE_H
 
 #include <pmg_wave.h> /* -I csrc (gfx950) or -I tests/emu (CPU emulator) */
+#include "pmg_wave.h" /* the shipped header by name: its matrix-pipe section, which carries its own emulator branch */
 #include "../../include/pmg.h"
 #include "../../include/pmg_model.h"
 

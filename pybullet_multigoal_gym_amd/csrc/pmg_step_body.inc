@@ -473,6 +473,14 @@ __device__ __forceinline__ void prepare_rows(ContactLds<NB, MAXC>& L, const floa
 #ifndef PMG_ROWSPACE
 #define PMG_ROWSPACE 1
 #endif
+/* PMG_ROWSPACE_MFMA: reach_contact_pgs_rowspace takes M^-1 J^T and the 24 x 24 coupling table from two chains of five
+ * v_mfma_f32_32x32x2_f32 (wv::mfma_32x32x2) instead of ~500 VALU instructions on wavefront 0's serial chain; 0 keeps the
+ * VALU build.  Measured on one MI355X (profiles/r07_reach_mfma_ab.txt): set-up 4197 -> 3452 cycles per contact substep (response +
+ * coefficients 2501 -> 1717), the pressed env alone 0.831 -> 0.775 ms, headline 4.685 -> 4.906 M env-steps/s (+ 4.7 %, four
+ * alternating runs each, spreads 0.1 %). */
+#ifndef PMG_ROWSPACE_MFMA
+#define PMG_ROWSPACE_MFMA 1
+#endif
 #ifndef PMG_PRE_SWEEP
 #define PMG_PRE_SWEEP 1
 #endif
@@ -491,13 +499,18 @@ __device__ __forceinline__ void ld9(const float* p, float* v)
     const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w; v[8] = p[8];
 }
+/* what the set-up leaves in a lane: its coefficient per source row (row lanes: -(J_j M^-1 J_s^T) / den_j, 0 for its own row; DoF
+ * lanes: (M^-1 J_s^T)_l), and, in a row lane, its response M^-1 J_j^T, diagonal, right-hand side, friction coefficient and bound */
+template <int NR>
+struct ReachRowSet {
+    float c24[NR], Rm[NJ];
+    float den, dinv, rhs, mu, hi;
+};
+/* (mc: in, the motor / limit state of the DoF lanes; out, the same with the row lanes' answers to a joint-space impulse added) */
 template <int NB, int MAXC>
-__device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>& L, int nc, NcRows& r, const McState& mc_in, const float* minv, float qd,
-                                                           float& dv, bool pre = false, float dv_pre = 0.f)
+__device__ __forceinline__ void reach_rowspace_setup(ContactLds<NB, MAXC>& L, int nc, const NcRows& r, McState& mc, const float* minv, float qd, float dv_pre,
+                                                     ReachRowSet<3 * MAXC>& w)
 {
-    /* pre: iteration 0's pass over the motor / limit rows has been made already (substep(), while the helper wavefront was
-     * colliding); dv_pre = the joint velocity change it left.  The contact rows then start from u = rhs - (J dv_pre) / den,
-     * i.e. their right-hand sides are taken at the joint velocity qd + dv_pre. */
     /* The rows are set up HERE, one per lane, straight from the contact list -- prepare_rows / build_contact_rows (four
      * LDS phases shaped for objects) are skipped on this path.  [BULLET-PRIOR] setupMultiBodyContactConstraint, as
      * build_contact_rows: finger (body A) x table: J_d = (w_d x p + v_d) . dir for the arm joints and the finger's own. */
@@ -552,11 +565,64 @@ __device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>&
     PMG_STAMP(tb_, 22);          /* contact fetch + Jacobian rows */
 #endif
     float Rm[NJ], denom = 0.f, rel = 0.f;
+    constexpr bool MM = PMG_ROWSPACE_MFMA && NB == 0 && MAXC == 8;   /* (every other instantiation of this template is dead code) */
+    float cq[24];
+    if constexpr (MM) {
+    /* The two dense products of the set-up on the matrix pipe (wv::mfma_32x32x2, exact f32): R^T = M^-1 J^T, (9 x 9)(9 x 24),
+     * then C = J R^T, (24 x 9)(9 x 24), one 32 x 32 tile each, K = 9 as the pairs (d, d + 4), d < 4, then (8, pad): lane
+     * (col, half) = l & 31, l >> 5 feeds entry 4 half + i of its row in step i.  The SAME five registers -- J_col[4 half + i],
+     * J_col[8] -- are the B operand of the first product and the A operand of the second, and result register i of the first
+     * (R_col[i + 4 half]; register 4: R_col[8], and an exact 0 in the upper half: row 12 of a product whose A rows >= 9
+     * are zeros) is the second's B operand as it stands.  Rows, columns and k beyond 9 / 24 are exact zeros.
+     * The results go back through the row store, which is this wavefront's from barrier B to the next barrier A: a table
+     * T[owner][28], owner l < 9 = DoF lane l holding R_s[l], s < 24 (the transposed read of R^T), owner 9 + j = row lane
+     * 16 + j holding C[s][j] -- 33 x 28 floats over the dead Jacobian slots.  Every lane then reads its 24 coefficients with
+     * the same six 16-byte reads; a row lane's Rm[d] is T[d][j], the very numbers the DoF lanes take as coefficients. */
+    static_assert(NJ == 9 && NR <= 24 && 3 * MAXC * ROW_STRIDE >= (NJ + 24) * 28, "row store too small for the coupling table");
+    float* T = slots;
+    {
+        const int col = l & 31, half = l >> 5;
+        const bool colv = col < NR, rowv = col < NJ;
+        const float* jp = slots + 12 * (colv ? col : 0);
+        const float* mp = &L.minv[rowv ? col : 0][0];
+        const float4 j4 = *(const float4*)(jp + 4 * half), m4 = *(const float4*)(mp + 4 * half);
+        const float j8 = jp[8], m8 = mp[8];
+        const float bj[5] = {colv ? j4.x : 0.f, colv ? j4.y : 0.f, colv ? j4.z : 0.f, colv ? j4.w : 0.f, (colv && half == 0) ? j8 : 0.f};
+        const float am[5] = {rowv ? m4.x : 0.f, rowv ? m4.y : 0.f, rowv ? m4.z : 0.f, rowv ? m4.w : 0.f, (rowv && half == 0) ? m8 : 0.f};
+        wv::acc16 R = wv::acc16_zero(), C = wv::acc16_zero();
+#pragma unroll
+        for (int i = 0; i < 5; i++) R = wv::mfma_32x32x2(am[i], bj[i], R);
+#pragma unroll
+        for (int i = 0; i < 5; i++) C = wv::mfma_32x32x2(bj[i], R[i], C);
+        WV::lds_sync();                                      /* every lane has its operands: the slots may go */
+        if (colv) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) T[28 * (4 * half + i) + col] = R[i];
+            if (half == 0) T[28 * 8 + col] = R[4];
+            float4* tc = (float4*)(T + 28 * (NJ + col) + 4 * half);   /* register 4 q + i: C[8 q + 4 half + i][col] */
+            tc[0] = make_float4(C[0], C[1], C[2], C[3]);
+            tc[2] = make_float4(C[4], C[5], C[6], C[7]);
+            tc[4] = make_float4(C[8], C[9], C[10], C[11]);
+        }
+        WV::lds_sync();
+        const bool rowl = rr >= 0 && rr < NR;
+        const float* tr = T + (rowl ? rr : 0);
+#pragma unroll
+        for (int d = 0; d < NJ; d++) Rm[d] = tr[28 * d];
+        const float4* tq = (const float4*)(T + 28 * (is_dof ? l : (rowl ? NJ + rr : 0)));
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            const float4 v = tq[q];
+            cq[4 * q] = v.x; cq[4 * q + 1] = v.y; cq[4 * q + 2] = v.z; cq[4 * q + 3] = v.w;
+        }
+    }
+    } else {
 #pragma unroll
     for (int i = 0; i < NJ; i++) {
         float mi[NJ];
         ld9(L.minv[i], mi);
         Rm[i] = ((Jm[0] * mi[0] + Jm[1] * mi[1]) + (Jm[2] * mi[2] + Jm[3] * mi[3])) + ((Jm[4] * mi[4] + Jm[5] * mi[5]) + (Jm[6] * mi[6] + Jm[7] * mi[7])) + Jm[8] * mi[8];
+    }
     }
     {
         float qv[NJ];
@@ -577,7 +643,6 @@ __device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>&
 #ifdef PMG_PROFILE
     PMG_STAMP(tb_, 23);          /* M^-1 J^T, diagonal, right-hand side */
 #endif
-    McState mc = mc_in;
     /* Coefficients.  Row lane 16 + j needs -(J_j . M^-1 J_s^T) / den_j for every source row s, DoF lane l < 9 needs
      * (M^-1 J_s^T)_l.  M^-1 is symmetric, so both are ONE formula: a . J_s with a = M^-1 J_j^T (a row lane's own response,
      * in registers) or a = row l of M^-1 (a DoF lane's own registers), scaled by -1 / den_j or 1 -- the same straight-line
@@ -586,9 +651,6 @@ __device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>&
      * the select and emitted a divergent branch per source row -- exec masks reloaded from spilled SGPRs, load -> wait ->
      * use with nothing in flight: 183 cycles per source, 4.4 k of the 7.3 k cycles of the set-up.)  A DoF lane's sum has
      * the terms and the association of the Rm[] above, i.e. the numbers lane s used to publish. */
-    float av[NJ];
-#pragma unroll
-    for (int k = 0; k < NJ; k++) av[k] = is_dof ? minv[k] : Rm[k];
     const float kk = is_dof ? 1.f : -dinv_r;
 #pragma unroll
     for (int D = 0; D < NJ; D++) {                           /* a contact row's answer to the joint-space impulse of DoF D */
@@ -596,7 +658,14 @@ __device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>&
         mc.A[D] = is_dof ? mc.A[D] : aD;
         mc.sgnw[D] = is_dof ? mc.sgnw[D] : aD * r.sg_l;
     }
-    float c24[NR];
+    float (&c24)[NR] = w.c24;
+    if constexpr (MM) {          /* PMG_ROWSPACE_MFMA: both tables came off the matrix pipe above; a DoF lane's entry is R_s[l] itself (kk = 1) */
+#pragma unroll
+        for (int s = 0; s < NR; s++) c24[s] = s == rr ? 0.f : kk * cq[s];
+    } else {
+    float av[NJ];
+#pragma unroll
+    for (int k = 0; k < NJ; k++) av[k] = is_dof ? minv[k] : Rm[k];
     int off = 0;
 #pragma unroll
     for (int s = 0; s < NR; s++) {
@@ -607,8 +676,31 @@ __device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>&
         const float d = ((av[0] * js[0] + av[1] * js[1]) + (av[2] * js[2] + av[3] * js[3])) + ((av[4] * js[4] + av[5] * js[5]) + (av[6] * js[6] + av[7] * js[7])) + av[8] * js[8];
         c24[s] = s == rr ? 0.f : kk * d;
     }
+    }
 #ifdef PMG_PROFILE
     PMG_STAMP(tb_, 11);          /* coefficient build */
+#endif
+#pragma unroll
+    for (int d = 0; d < NJ; d++) w.Rm[d] = Rm[d];
+    w.den = (is_row && denom > SIMD_EPS) ? denom : 0.f;
+    w.dinv = dinv_r; w.rhs = rhs_r; w.mu = mu_r; w.hi = hi_r;
+}
+template <int NB, int MAXC>
+__device__ __forceinline__ void reach_contact_pgs_rowspace(ContactLds<NB, MAXC>& L, int nc, NcRows& r, const McState& mc_in, const float* minv, float qd,
+                                                           float& dv, bool pre = false, float dv_pre = 0.f)
+{
+    /* pre: iteration 0's pass over the motor / limit rows has been made already (substep(), while the helper wavefront was
+     * colliding); dv_pre = the joint velocity change it left.  The contact rows then start from u = rhs - (J dv_pre) / den,
+     * i.e. their right-hand sides are taken at the joint velocity qd + dv_pre. */
+    constexpr int NR = 3 * MAXC;
+    const int l = WV::lane_local();
+    const bool is_dof = l < NJ;
+    McState mc = mc_in;
+    ReachRowSet<NR> w;
+    reach_rowspace_setup<NB, MAXC>(L, nc, r, mc, minv, qd, dv_pre, w);
+    const float (&c24)[NR] = w.c24;
+    const float dinv_r = w.dinv, rhs_r = w.rhs, mu_r = w.mu, hi_r = w.hi;
+#ifdef PMG_PROFILE
     long long tprev = prof::now();
 #endif
     float x = is_dof ? dv_pre : rhs_r;                       /* DoF lanes: dv; row lanes: u (app = 0; dv = 0 or dv_pre at entry) */

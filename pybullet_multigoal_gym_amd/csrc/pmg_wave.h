@@ -591,3 +591,68 @@ __device__ __forceinline__ float sel_lane(float a, float b, int l, int lane_k) {
 
 }  // namespace wr
 #endif
+
+/* ---- the matrix pipe --------------------------------------------------------------------------------------------------
+ * Outside the guard above ON PURPOSE: the emulator's stand-in header (tests/emu/pmg_wave.h) defines PMG_WAVE_H too, so
+ * pmg_device.h includes THIS file a second time by its quoted name and the emulator build picks up the PMG_EMULATE branch
+ * below -- one definition of the primitive, next to its device form, for both builds.
+ *
+ * mfma_32x32x2(a, b, c): D = A B + C on one wavefront, v_mfma_f32_32x32x2_f32 -- A is 32 x 2, B is 2 x 32, C / D 32 x 32, all
+ * f32, exact: D[i][j] = fmaf(A[i][1], B[1][j], fmaf(A[i][0], B[0][j], C[i][j])), each fmaf rounded once, k = 0 first.
+ *   operands  lane l:      a = A[i = l & 31][k = l >> 5],   b = B[k = l >> 5][j = l & 31]     (one VGPR each)
+ *   result    lane l, register r (0..15):   D[i = 8 (r >> 2) + 4 (l >> 5) + (r & 3)][j = l & 31]
+ * i.e. lane j holds rows 0-3, 8-11, 16-19, 24-27 of column j in registers 0-3, 4-7, 8-11, 12-15, lane 32 + j rows 4-7,
+ * 12-15, 20-23, 28-31.  Register r of a result therefore IS a B operand: the pair of rows (r', r' + 4) with r' = 8 (r >> 2) +
+ * (r & 3) of every column, ready for a second product that contracts over those rows -- no data movement in between.
+ * The instruction runs for every lane whatever EXEC says: call it from wave-uniform control flow with all 64 lanes alive.
+ *
+ * Budget (why 32x32x2 and not 16x16x4) for the two products of the reach row set-up, (9 x 9)(9 x 24) and (24 x 9)(9 x 24):
+ * 32x32x2 covers either in ONE tile, K = 9 padded to 10: 5 + 5 instructions x 64 cycles = 640, one dependent chain per
+ * product (64-cycle dependent latency = the issue interval: nothing is lost to the chain).  16x16x4 needs 2 + 4 tiles x 3
+ * k-steps = 18 instructions x 32 cycles = 576 with four interleaved accumulators (40-cycle dependent latency), twelve result
+ * quads to route instead of two blocks: 64 cycles (0.3 % of a contact substep) for three times the bookkeeping.  32x32x2. */
+#ifndef PMG_WAVE_MFMA_H
+#define PMG_WAVE_MFMA_H
+namespace wv {
+#ifndef PMG_EMULATE
+typedef float acc16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ acc16 acc16_zero()
+{
+    acc16 z;
+#pragma unroll
+    for (int r = 0; r < 16; r++) z[r] = 0.f;
+    return z;
+}
+__device__ __forceinline__ acc16 mfma_32x32x2(float a, float b, acc16 c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+#else
+    return c;   /* (the host pass only parses this) */
+#endif
+}
+#else
+struct acc16 {
+    float v[16];
+    float& operator[](int r) { return v[r]; }
+    const float& operator[](int r) const { return v[r]; }
+};
+inline acc16 acc16_zero() { acc16 z; for (int r = 0; r < 16; r++) z.v[r] = 0.f; return z; }
+/* the same fmaf chain, k = 0 then k = 1, operands handed round through the exchange buffer */
+inline acc16 mfma_32x32x2(float a, float b, acc16 c)
+{
+    const float ab[2] = {a, b};
+    exchange_put<2>(ab);
+    const int l = lane(), j = l & 31, h = l >> 5;
+    for (int r = 0; r < 16; r++) {
+        const int i = 8 * (r >> 2) + 4 * h + (r & 3);
+        float d = c.v[r];
+        for (int k = 0; k < 2; k++) d = fmaf(xbuf()[32 * k + i], xbuf()[64 + 32 * k + j], d);
+        c.v[r] = d;
+    }
+    exchange_done();
+    return c;
+}
+#endif
+}  // namespace wv
+#endif

@@ -58,6 +58,13 @@ if 'FETCH_SIZE' in summary and 'WRITE_SIZE' in summary:
             if c.get('fetch_factor_dword') and c.get('write_factor_dword'):
                 cal = {'fetch_dword': c['fetch_factor_dword'], 'write_dword': c['write_factor_dword'], 'source': os.path.basename(cand)}
                 break
+    # PMG_CALIBRATION_TAG: without a calibration of this round, take the committed factors of another round (they belong to the part
+    # and the access width, not to the kernels of a round); the file that was used is named in the output either way
+    other = os.path.join(root, 'profiles', '%s_counter_calibration.json' % os.environ.get('PMG_CALIBRATION_TAG', tag))
+    if cal['source'].startswith('uncalibrated') and os.path.exists(other):
+        c = json.load(open(other))
+        if c.get('fetch_factor_dword') and c.get('write_factor_dword'):
+            cal = {'fetch_dword': c['fetch_factor_dword'], 'write_dword': c['write_factor_dword'], 'source': os.path.basename(other)}
     json.dump({'task': task, 'envs_per_gpu': N, 'kernel_source_sha16': SRC, 'library_sha16': LIB,
                'command': 'rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python bench.py --task %s --envs-per-gpu %d --steps 50 --warmup 5 --no-cpu-baseline --no-extras' % (task, N),
                'kernel': 'pmg_k_step family (+ redo)', 'FETCH_SIZE_KiB': fk, 'WRITE_SIZE_KiB': wk, 'calibration': cal,
