@@ -345,6 +345,7 @@ int pmgd_rowsetup(int n, const float* q, const float* qd, const float* con, cons
     return (int)d.err;
 }
 int pmgd_rowspace_mfma() { return PMG_ROWSPACE_MFMA; }
+int pmgd_rowsetup_pipeline() { return PMG_ROWSETUP_PIPELINE; }
 
 /* n cases: q, qd, tau [n][9] -> qdd [n][9], minv [n][81], tip [n][12] (position, rotation of the tip frame) */
 int pmgd_dynamics(int packed, int n, const float* q, const float* qd, const float* tau, float* qdd, float* minv_out, float* tip_out)

@@ -107,6 +107,7 @@ extern "C" int pmge_rowsetup(int n, const float* q, const float* qd, const float
     return 0;
 }
 extern "C" int pmge_rowspace_mfma() { return PMG_ROWSPACE_MFMA; }
+extern "C" int pmge_rowsetup_pipeline() { return PMG_ROWSETUP_PIPELINE; }
 extern "C" int pmge_mfma(int n, int steps, const float* a, const float* b, const float* c, float* out)
 {
     if (n < 1 || n > prim::MFMA_MAX_CASES || steps < 1 || steps > prim::MFMA_MAX_STEPS) return -1;

@@ -297,4 +297,7 @@ hipError_t pmg_launch_reset(const pmg::EnvParams& P, const unsigned char* d_mask
     hipLaunchKernelGGL(pmg_k_reset, dim3(P.n_envs), dim3(64), 0, s, P, d_mask, done_only);
     return hipGetLastError();
 }
+/* the setting of PMG_ROWSETUP_PIPELINE the kernels above were built with: A/B builds and the tests that compare the two settings
+ * tell their libraries apart by it (a build diagnostic, not part of include/pmg.h) */
+extern "C" int pmg_rowsetup_pipeline(void) { return PMG_ROWSETUP_PIPELINE; }
 #include "pmg_learner_body.inc"   /* the learner side: rewards, running normaliser, policy-input rows, HER minibatches */

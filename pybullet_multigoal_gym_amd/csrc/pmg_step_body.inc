@@ -481,6 +481,28 @@ __device__ __forceinline__ void prepare_rows(ContactLds<NB, MAXC>& L, const floa
 #ifndef PMG_ROWSPACE_MFMA
 #define PMG_ROWSPACE_MFMA 1
 #endif
+/* PMG_ROWSETUP_PIPELINE: the front of reach_rowspace_setup (contact fetch, plane_space, direction, Jacobian entries) without its
+ * stalls; 0 keeps that code as it was.  Same arithmetic, same bits (tests/rowsetup_pipelined_cases.py).  The stalls were not the
+ * ones expected: in the =0 build the eighteen reads of the joint subspaces are ALREADY in flight together behind one wait (the
+ * compiler unrolls the loop and hoists them).  What its ISA shows instead (profiles/r08_reach_setup_ab.txt, section 1):
+ *   - the direction select `tt == 0 ? n : (tt == 1 ? t1 : t2)` behind plane_space's if / else comes out as a cascade of 19 branches
+ *     over exec masks, 100 instructions of which 85 scalar, that a wavefront with rows of all three kinds walks arm by arm;
+ *   - the subspace reads sit BEHIND that cascade and the contact fetch is waited for in front of it: two exposed LDS latencies;
+ *   - the friction coefficient is read under a branch at the very end of the set-up and waited for at once: a third.
+ * With the switch on, the operands of each select are plain locals -- clang then emits a select, and nothing is left for the
+ * optimiser to thread a branch through: six v_cndmask --, the subspaces of the first PMG_ROWSETUP_PREFETCH joints are read right
+ * behind the contact, in front of plane_space (the wait there is for the contact alone; the rest are read where they were, behind
+ * the first joints' arithmetic), and the friction coefficient rides with the contact fetch.  Prefetch depth 6, not 9: from 7 on
+ * pmg_k_step_reach2 takes a tenth VGPR spill (9 at depth <= 6 as without the switch), and 6 measured fastest of 0 / 6 / 9.
+ * Measured on one MI355X (same note): the set-up's front 1569 -> about 1.1 k cycles per contact substep on the stamped one-wavefront
+ * kernel, headline + 1 % (four alternating runs each; the slowest new run beats the fastest parent run by more than both spreads).
+ * The M^-1 store needed nothing: the compiler already writes the nine floats as two 16-byte stores and a dword. */
+#ifndef PMG_ROWSETUP_PIPELINE
+#define PMG_ROWSETUP_PIPELINE 1
+#endif
+#ifndef PMG_ROWSETUP_PREFETCH
+#define PMG_ROWSETUP_PREFETCH 6      /* joints (0 .. 9) whose subspace is read in front of plane_space */
+#endif
 #ifndef PMG_PRE_SWEEP
 #define PMG_PRE_SWEEP 1
 #endif
@@ -532,17 +554,44 @@ __device__ __forceinline__ void reach_rowspace_setup(ContactLds<NB, MAXC>& L, in
         const float4 a = *(const float4*)L.con[cc], b = *(const float4*)(L.con[cc] + 4), c4 = *(const float4*)(L.con[cc] + 8);
         o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w; o[8] = c4.x; o[9] = c4.y; o[10] = c4.z; o[11] = c4.w;
     }
+    constexpr bool PIPE = PMG_ROWSETUP_PIPELINE != 0;
+    float mu_c = 0.f;                                        /* PIPE: the contact's friction coefficient rides with the contact fetch */
+    if constexpr (PIPE) mu_c = L.con_mu[cc];
+    float Sv[NJ][6];                                         /* PIPE: the subspaces of the first NPRE joints, read behind the contact and in front of plane_space */
+    constexpr int NPRE = PIPE ? PMG_ROWSETUP_PREFETCH : 0;
+    static_assert(NPRE >= 0 && NPRE <= NJ, "PMG_ROWSETUP_PREFETCH counts joints");
+    {
+#pragma unroll
+        for (int d = 0; d < NPRE; d++) {                     /* uniform address: LDS broadcast */
+            const float4 a = *(const float4*)L.S[d], b = *(const float4*)(L.S[d] + 4);
+            Sv[d][0] = a.x; Sv[d][1] = a.y; Sv[d][2] = a.z; Sv[d][3] = a.w; Sv[d][4] = b.x; Sv[d][5] = b.y;
+        }
+    }
     const float pt[3] = {o[2], o[3], o[4]}, n[3] = {o[8], o[9], o[10]};
     const int own = (int)o[0] == BODY_FINGER1 ? 7 : 8;
     float t1[3], t2[3], dir[3];
     plane_space(n, t1, t2);
 #pragma unroll
-    for (int k = 0; k < 3; k++) dir[k] = tt == 0 ? n[k] : (tt == 1 ? t1[k] : t2[k]);
+    for (int k = 0; k < 3; k++) {
+        if constexpr (PIPE) {                                /* selects of plain locals: v_cndmask, not branches */
+            const float nk = n[k], t1k = t1[k], t2k = t2[k];
+            const float tk = tt == 1 ? t1k : t2k;
+            dir[k] = tt == 0 ? nk : tk;
+        } else {
+            dir[k] = tt == 0 ? n[k] : (tt == 1 ? t1[k] : t2[k]);
+        }
+    }
+#ifdef PMG_PROFILE
+    PMG_STAMP(tb_, 13);          /* M^-1 / qd stores, contact fetch, plane_space, direction select */
+#endif
     float Jm[NJ];
 #pragma unroll
     for (int d = 0; d < NJ; d++) {
         float S[8];                                          /* uniform address: LDS broadcast */
-        {
+        if (d < NPRE) {
+#pragma unroll
+            for (int a = 0; a < 6; a++) S[a] = Sv[d][a];
+        } else {
             const float4 a = *(const float4*)L.S[d], b = *(const float4*)(L.S[d] + 4);
             S[0] = a.x; S[1] = a.y; S[2] = a.z; S[3] = a.w; S[4] = b.x; S[5] = b.y;
         }
@@ -551,6 +600,9 @@ __device__ __forceinline__ void reach_rowspace_setup(ContactLds<NB, MAXC>& L, in
         const float jd = (v[0] + S[3]) * dir[0] + (v[1] + S[4]) * dir[1] + (v[2] + S[5]) * dir[2];
         Jm[d] = (is_row && (d < 7 || d == own)) ? jd : 0.f;
     }
+#ifdef PMG_PROFILE
+    PMG_STAMP(tb_, 15);          /* the nine Jacobian entries */
+#endif
     /* every row lane leaves its Jacobian in a 12-float slot of the (free) row storage; the slots of rows that do not exist
      * hold zeros (Jm is zero there), so that nothing below has to branch on the contact count */
     float* slots = &L.rows[0][0];
@@ -562,7 +614,7 @@ __device__ __forceinline__ void reach_rowspace_setup(ContactLds<NB, MAXC>& L, in
     }
     WV::lds_sync();
 #ifdef PMG_PROFILE
-    PMG_STAMP(tb_, 22);          /* contact fetch + Jacobian rows */
+    PMG_STAMP(tb_, 22);          /* slot store + lds_sync (13 + 15 + 22: contact fetch + Jacobian rows) */
 #endif
     float Rm[NJ], denom = 0.f, rel = 0.f;
     constexpr bool MM = PMG_ROWSPACE_MFMA && NB == 0 && MAXC == 8;   /* (every other instantiation of this template is dead code) */
@@ -639,7 +691,10 @@ __device__ __forceinline__ void reach_rowspace_setup(ContactLds<NB, MAXC>& L, in
         else pos_err = -dist * CONTACT_ERP / DT;
         rhs_r = is_row ? (tt == 0 ? (pos_err + vel_err) * dinv_r : -rel * dinv_r) : 0.f;
     }
-    const float mu_r = is_row ? L.con_mu[cc] : 0.f, hi_r = is_row ? 1e10f : 0.f;
+    float mu_r;
+    if constexpr (PIPE) mu_r = is_row ? mu_c : 0.f;          /* (=0: a read under a branch at the very end, waited for at once) */
+    else mu_r = is_row ? L.con_mu[cc] : 0.f;
+    const float hi_r = is_row ? 1e10f : 0.f;
 #ifdef PMG_PROFILE
     PMG_STAMP(tb_, 23);          /* M^-1 J^T, diagonal, right-hand side */
 #endif
