@@ -3,13 +3,16 @@
  * (Makefile), so that tests/test_gpu_wave_primitives.py and tests/test_gpu_device_functions.py can compare each of them
  * with its model / the float64 oracle directly instead of through a whole rollout.  Never part of the product.
  *
- * Every probe is ONE workgroup, finite, and masks every index it derives from its arguments; every exported function
- * allocates, launches on the null stream, synchronises, copies back and returns the HIP status (< 0: bad arguments).
+ * Every probe is finite and masks every index it derives from its arguments, and every probe but one is ONE workgroup: the plan
+ * probe (pmgd_plan) runs the grids of pmg_launch_plan, up to ceil(131 072 / 1024) = 128 workgroups of 1024 threads at its largest
+ * batch (65 for the 65 792 envs the tests go to).  Every exported function allocates, launches on the null stream, synchronises,
+ * copies back and returns the HIP status (< 0: bad arguments, nothing launched).
  * Built twice: as is (the inline-asm DPP paths that ship) and with -DPMG_NO_R0_DPP -DPMG_NO_DPP_FMAC -DPMG_NO_NEWBCAST
  * (the plain C++ branches of the same header), same symbols, two libraries. */
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "pmg_kernels.h"   /* (pmg_contact.h, and the step bodies for the reach row set-up) */
+#include "pmg_plan_probe.inc"
 
 #define WV wv
 #define PRIM_FN prim_probe_wv
@@ -281,6 +284,13 @@ __global__ void __launch_bounds__(64) k_double_maths(int op, int n, const double
     }
 }
 
+
+/* ---- the launch plan: the product's four plan kernels under other names, same bounds, same bodies (pmg_kernels.hip) -------- */
+__global__ void __launch_bounds__(1024) k_plan(pmg::EnvParams P, const float* __restrict__ actions) { pmg::plan_all(P, actions); }
+__global__ void __launch_bounds__(1024) k_plan_reach(pmg::EnvParams P, const float* __restrict__ actions) { pmg::plan_all<true>(P, actions); }
+__global__ void __launch_bounds__(1024) k_plan_count(pmg::EnvParams P, const float* __restrict__ actions) { pmg::plan_count(P, actions); }
+__global__ void __launch_bounds__(1024) k_plan_scatter(pmg::EnvParams P, const float* __restrict__ actions) { pmg::plan_scatter(P, actions); }
+
 }  // namespace
 
 extern "C" {
@@ -471,6 +481,39 @@ int pmgd_double_maths(int op, int n, const double* x, const double* y, double* o
     if (d.err == hipSuccess) hipLaunchKernelGGL(k_double_maths, dim3(1), dim3(64), 0, 0, op, n, dx, dy, d0, d1);
     d.sync();
     d.down(o0, d0, (size_t)n); d.down(o1, d1, (size_t)n);
+    return (int)d.err;
+}
+
+/* The plan on the caller's buffer: pmge_plan of tests/emu/pmg_probe.cpp on the device (arguments and their check: pmg_plan_probe.inc).
+ * mode 0: pmg_k_plan's body in one workgroup, 1: pmg_k_plan_reach's, 2: pmg_k_plan_count + pmg_k_plan_scatter over ceil(N / 1024)
+ * workgroups -- the grids of pmg_launch_plan.  buf: [guard | Sched::words(N) | guard], in and out; every device array is sized
+ * from the checked arguments and Sched::words */
+int pmgd_plan(int mode, int n_envs, int nb, int chest, int joint_control, float near_r, float chest_reach, int fd_div, int wave_budget, int lpt_thresh, int lpt_permille,
+              int lpt_parity, const int* env_cycles, int* lpt_state, const float* hot, const float* blocks, const float* actions, int adim, int guard, int* buf)
+{
+    if (!plan_args_ok(mode, n_envs, nb, chest, joint_control, lpt_thresh, lpt_permille, lpt_parity, env_cycles, lpt_state, hot, blocks, actions, adim, guard, buf)) return -1;
+    const size_t N = (size_t)n_envs, words = pmgx::Sched::words(N) + 2 * (size_t)guard;
+    pmg::EnvParams P = plan_params(n_envs, nb, chest, joint_control, near_r, chest_reach, fd_div, wave_budget, lpt_thresh, lpt_permille, lpt_parity, adim);
+    Dev d;
+    P.hot = const_cast<float*>(d.up(hot, N * pmg::HOT_DIM));
+    P.blocks = nb > 0 ? const_cast<float*>(d.up(blocks, N * pmg::BLOCK_DIM * (size_t)nb)) : nullptr;
+    const float* dact = d.up(actions, N * (size_t)adim);
+    P.env_cycles = env_cycles ? const_cast<int*>(d.up(env_cycles, 2 * N)) : nullptr;
+    P.lpt_state = lpt_state ? d.up(lpt_state, (size_t)(2 + pmg::LPT_BINS)) : nullptr;
+    int* dbuf = d.up(buf, words);
+    P.sched = dbuf + guard;
+    if (d.err == hipSuccess) {
+        const int nwg = (n_envs + pmg::PLAN_THREADS - 1) / pmg::PLAN_THREADS;
+        if (mode == 0) hipLaunchKernelGGL(k_plan, dim3(1), dim3(pmg::PLAN_THREADS), 0, 0, P, dact);
+        else if (mode == 1) hipLaunchKernelGGL(k_plan_reach, dim3(1), dim3(pmg::PLAN_THREADS), 0, 0, P, dact);
+        else {
+            hipLaunchKernelGGL(k_plan_count, dim3(nwg), dim3(pmg::PLAN_THREADS), 0, 0, P, dact);
+            hipLaunchKernelGGL(k_plan_scatter, dim3(nwg), dim3(pmg::PLAN_THREADS), 0, 0, P, dact);
+        }
+    }
+    d.sync();
+    d.down(buf, dbuf, words);
+    if (lpt_state) d.down(lpt_state, P.lpt_state, (size_t)(2 + pmg::LPT_BINS));
     return (int)d.err;
 }
 

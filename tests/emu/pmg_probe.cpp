@@ -185,6 +185,35 @@ extern "C" int pmge_probe_plan(int n_envs, int nb, const float* hot, const float
     return P.schedule().promoted();                         /* 0 / 1: the word pmg_k_step_list reads for its issue priority */
 }
 
+/* The plan with every parameter it reads, on the caller's own buffer (tests/plan_cases.py; pmgd_plan of gpu_probe/ is the same call
+ * on the device).  mode 0: plan_all, 1: plan_all<true> (reach under tip control), 2: plan_count + plan_scatter over ceil(N / 1024)
+ * workgroups.  buf: [guard | Sched::words(N) | guard] ints, in and out -- the plan works on the words in the middle, the caller
+ * fills all of it with a sentinel and sees what was written.  env_cycles: [N, 2] or NULL; lpt_state: [2 + LPT_BINS], in and out, or
+ * NULL.  The table and the clip box of the tip target are every task's but slide's.  Returns 0, or < 0 for arguments the plan
+ * would read or write out of these arrays with (nothing is run then) */
+#include "../../gpu_probe/pmg_plan_probe.inc"
+extern "C" int pmge_plan(int mode, int n_envs, int nb, int chest, int joint_control, float near_r, float chest_reach, int fd_div, int wave_budget, int lpt_thresh,
+                         int lpt_permille, int lpt_parity, const int* env_cycles, int* lpt_state, const float* hot, const float* blocks, const float* actions, int adim,
+                         int guard, int* buf)
+{
+    using namespace pmg;
+    if (!plan_args_ok(mode, n_envs, nb, chest, joint_control, lpt_thresh, lpt_permille, lpt_parity, env_cycles, lpt_state, hot, blocks, actions, adim, guard, buf)) return -1;
+    EnvParams P = plan_params(n_envs, nb, chest, joint_control, near_r, chest_reach, fd_div, wave_budget, lpt_thresh, lpt_permille, lpt_parity, adim);
+    P.hot = const_cast<float*>(hot);
+    P.blocks = const_cast<float*>(blocks);
+    P.env_cycles = const_cast<int*>(env_cycles);
+    P.lpt_state = lpt_state;
+    P.sched = buf + guard;
+    const int nwg = (n_envs + PLAN_THREADS - 1) / PLAN_THREADS;
+    if (mode == 0) emu::launch(1, PLAN_THREADS, [&]() { plan_all(P, actions); });
+    else if (mode == 1) emu::launch(1, PLAN_THREADS, [&]() { plan_all<true>(P, actions); });
+    else {
+        emu::launch(nwg, PLAN_THREADS, [&]() { plan_count(P, actions); });
+        emu::launch(nwg, PLAN_THREADS, [&]() { plan_scatter(P, actions); });
+    }
+    return 0;
+}
+
 /* The wavefront-order detector's own probes (tests/test_wave_order.py; emulator only): 128 threads, wavefront 1 hands one LDS word to
  * wavefront 0 between two workgroup barriers.  _racy: nothing orders the write and the read -- what wavefront 0 sees depends on
  * which wavefront runs first, and the orders 01 and 10 must tell.  _fenced: a barrier between them -- every order agrees.
