@@ -74,6 +74,21 @@ class PmgTd3Target(C.Structure):
                 ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
 
 
+class PmgSacSample(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('ls_lo', C.c_float), ('ls_hi', C.c_float), ('sample', C.c_int32), ('reserved2', C.c_int32),
+                ('seed', C.c_uint64), ('counter', C.c_uint64), ('row_offset', C.c_int64), ('batch', C.c_int64), ('d_x', C.c_void_p), ('x_stride', C.c_int64),
+                ('d_action', C.c_void_p), ('action_stride', C.c_int64), ('d_logp', C.c_void_p), ('d_noise', C.c_void_p), ('noise_stride', C.c_int64),
+                ('d_preact', C.c_void_p), ('preact_stride', C.c_int64)]
+
+
+class PmgSacTarget(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gamma', C.c_float), ('clip_lo', C.c_float), ('clip_hi', C.c_float), ('alpha', C.c_float),
+                ('ls_lo', C.c_float), ('ls_hi', C.c_float), ('sample', C.c_int32), ('reserved2', C.c_int32), ('seed', C.c_uint64), ('counter', C.c_uint64),
+                ('row_offset', C.c_int64), ('batch', C.c_int64), ('d_alpha', C.c_void_p), ('d_x_next', C.c_void_p), ('x_stride', C.c_int64),
+                ('d_reward', C.c_void_p), ('d_terminal', C.c_void_p), ('d_y', C.c_void_p), ('d_q_min', C.c_void_p), ('d_q1', C.c_void_p), ('d_q2', C.c_void_p),
+                ('d_next_action', C.c_void_p), ('d_logp', C.c_void_p), ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
+
+
 class PmgMlpParams(C.Structure):
     _fields_ = [('d_weight', C.c_void_p * 4), ('d_bias', C.c_void_p * 4)]
 
@@ -120,7 +135,8 @@ class PmgLibrary:
                'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
                'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
                'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device',
-               'pmg_td3_target_work_floats', 'pmg_td3_target_device']
+               'pmg_td3_target_work_floats', 'pmg_td3_target_device',
+               'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -145,6 +161,7 @@ class PmgLibrary:
         L.pmg_mlp_grad_chunked_work_floats.restype = C.c_int64
         L.pmg_policy_grad_work_floats.restype = C.c_int64
         L.pmg_td3_target_work_floats.restype = C.c_int64
+        L.pmg_sac_target_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -408,6 +425,41 @@ class PmgHandle:
     def td3_target_device(self, actor_target, critic1_target, critic2_target, td):
         """y = clip(r + gamma min(Q1', Q2')(x', smoothed pi'(x'))) of a td3_struct(); critic2_target may be None; stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_td3_target_device(self.h, C.byref(actor_target), C.byref(critic1_target),
+                                                     C.byref(critic2_target) if critic2_target is not None else None, C.byref(td)))
+
+    # -- SAC: the Gaussian head and the soft target (include/pmg.h, DESIGN.md 3.15) --
+    @staticmethod
+    def sac_sample_struct(batch, d_x, x_stride, d_action=None, action_stride=0, d_logp=None, d_noise=None, noise_stride=0, d_preact=None, preact_stride=0,
+                          ls_lo=-20.0, ls_hi=2.0, sample=1, seed=0, counter=0, row_offset=0):
+        """pmg_sac_sample from device pointers (integers or None); pmg_sac_act_env_device does not read batch, d_x, x_stride and row_offset."""
+        return PmgSacSample(C.sizeof(PmgSacSample), 0, ls_lo, ls_hi, int(bool(sample)), 0, seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), row_offset, batch,
+                            d_x, x_stride, d_action, action_stride, d_logp, d_noise, noise_stride, d_preact, preact_stride)
+
+    def sac_sample_device(self, actor, s):
+        """action, log-probability, noise and pre-activations of a Gaussian actor on the rows of a sac_sample_struct(); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_sac_sample_device(self.h, C.byref(actor), C.byref(s)))
+
+    def sac_act_env_device(self, actor, state_kind, s):
+        """the same on the rows of the last step / reset (the outputs and the head's settings of a sac_sample_struct()); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_sac_act_env_device(self.h, C.byref(actor), C.c_int(state_kind), C.byref(s)))
+
+    @staticmethod
+    def sac_target_struct(batch, d_x_next, x_stride, d_reward, d_y, gamma, clip_lo=-float('inf'), clip_hi=float('inf'), alpha=0.0, ls_lo=-20.0, ls_hi=2.0,
+                          sample=1, seed=0, counter=0, row_offset=0, d_alpha=None, d_terminal=None, d_q_min=None, d_q1=None, d_q2=None, d_next_action=None,
+                          d_logp=None, d_work=None, work_floats=0):
+        """pmg_sac_target from device pointers (integers or None)."""
+        return PmgSacTarget(C.sizeof(PmgSacTarget), 0, gamma, clip_lo, clip_hi, alpha, ls_lo, ls_hi, int(bool(sample)), 0, seed & (2 ** 64 - 1),
+                            counter & (2 ** 64 - 1), row_offset, batch, d_alpha, d_x_next, x_stride, d_reward, d_terminal, d_y, d_q_min, d_q1, d_q2,
+                            d_next_action, d_logp, d_work, work_floats)
+
+    def sac_target_work_floats(self, actor, has_next_action, batch):
+        """floats of workspace pmg_sac_target_device needs: batch * A without d_next_action, else 0 (< 0: invalid)"""
+        return int(self.L.lib.pmg_sac_target_work_floats(C.byref(actor), C.c_int(bool(has_next_action)), C.c_int64(batch)))
+
+    def sac_target_device(self, actor, critic1_target, critic2_target, td):
+        """y = clip(r + gamma (min(Q1', Q2')(x', a') - alpha log pi(a' | x'))) of a sac_target_struct(); critic2_target may be None; stream-ordered, no
+        host sync."""
+        self._check(self.L.lib.pmg_sac_target_device(self.h, C.byref(actor), C.byref(critic1_target),
                                                      C.byref(critic2_target) if critic2_target is not None else None, C.byref(td)))
 
     # -- back-propagation, Adam, Polyak (include/pmg.h, DESIGN.md 3.11) --

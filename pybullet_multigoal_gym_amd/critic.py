@@ -43,6 +43,9 @@ three Polyak updates on every ``policy_delay``-th update only -- a host-side ``i
 The smoothed action both target critics saw goes to ``d_next_action`` [B, A]; without it the call keeps it in ``d_work``
 (``td3_target_work_floats`` floats).  The noise of row b is a function of ``(seed, counter, row_offset + b)``, so a batch cut into pieces
 (``row_offset`` = the piece's first row) gives the rows of the whole.  ``critic2 = None, sigma = 0`` is ``td_target_device``, bit for bit.
+
+SAC takes ``sac_target_device`` with a ``sac.GaussianActor`` (the online one) in the actor's place: the sampled action, its
+log-probability and ``y = clip(r + gamma (min(Q1', Q2')(x', a') - alpha log pi(a' | x')))`` in one call; the update recipe is in ``sac.py``.
 """
 import numpy as np
 
@@ -244,6 +247,90 @@ class Critic(Trainable):
             for p in ptrs:
                 h.device_free(p)
         return y, qm, q1, q2, na
+
+    def _gaussian_actor(self, actor):
+        from .sac import GaussianActor
+        if not isinstance(actor, GaussianActor):
+            raise ValueError('actor must be a GaussianActor (SAC: the online one), not %r' % (type(actor),))
+        mlp = actor._loaded()
+        if actor.widths[0] + actor.widths[-1] // 2 != self.widths[0]:
+            raise ValueError('the actor maps %d -> 2 * %d, the critic takes %d inputs' % (actor.widths[0], actor.widths[-1] // 2, self.widths[0]))
+        return mlp
+
+    def sac_target_work_floats(self, actor, batch, next_action=False):
+        """floats of workspace ``sac_target_device`` needs: batch * A without d_next_action, else 0."""
+        self._loaded()
+        return self._h.sac_target_work_floats(self._gaussian_actor(actor), next_action, int(batch))
+
+    def sac_target_device(self, actor, critic2, d_x_next, d_reward, d_y, gamma, clip_lo, clip_hi, alpha, sample=True, seed=0, counter=0, row_offset=0,
+                          ls_lo=-20.0, ls_hi=2.0, d_alpha=None, d_terminal=None, d_q_min=None, d_q1=None, d_q2=None, d_next_action=None, d_logp=None,
+                          d_work=None, work_floats=0, x_stride=None, *, batch):
+        """SAC's soft target in one call (DESIGN.md 3.15): d_y [batch] = clip(r + gamma (min(Q1', Q2')(x', a') - alpha log pi(a' | x'))), a' and
+        log pi sampled from the GaussianActor ``actor`` (SAC: the online one), with this network as Q1' and ``critic2``'s as Q2' (None: one
+        critic).  ``d_alpha``: one float in device memory that replaces ``alpha`` (a learned temperature without a host sync).  The draws are a
+        function of (seed, counter, row_offset + row, column); sample=False: the mode.  d_terminal, d_q_min, d_q1, d_q2, d_logp [batch] and
+        d_next_action [batch, A] (a') are optional.  Without d_next_action, d_work holds at least ``sac_target_work_floats`` floats.
+        Allocates nothing; on the handle's stream, no host sync."""
+        mlp = self._loaded()
+        amlp = self._gaussian_actor(actor)
+        mlp2 = self._twin(critic2)
+        gamma, clip_lo, clip_hi, alpha, ls_lo, ls_hi = float(gamma), float(clip_lo), float(clip_hi), float(alpha), float(ls_lo), float(ls_hi)
+        if not gamma >= 0.0 or not np.isfinite(gamma):
+            raise ValueError('gamma %r must be finite and >= 0' % (gamma,))
+        if not clip_lo <= clip_hi:
+            raise ValueError('clips %r / %r must be ordered and not NaN' % (clip_lo, clip_hi))
+        if not alpha >= 0.0 or not np.isfinite(alpha):
+            raise ValueError('alpha %r must be finite and >= 0' % (alpha,))
+        if not (np.isfinite(ls_lo) and np.isfinite(ls_hi) and ls_lo <= ls_hi):
+            raise ValueError('ls_lo %r / ls_hi %r must be finite and ordered' % (ls_lo, ls_hi))
+        if int(row_offset) < 0:
+            raise ValueError('row_offset %r must be >= 0' % (row_offset,))
+        h = self._h
+        td = h.sac_target_struct(int(batch), d_x_next, actor.widths[0] if x_stride is None else x_stride, d_reward, d_y, gamma, clip_lo, clip_hi, alpha, ls_lo,
+                                 ls_hi, bool(sample), int(seed), int(counter), int(row_offset), d_alpha, d_terminal, d_q_min, d_q1, d_q2, d_next_action, d_logp,
+                                 d_work, int(work_floats))
+        h.sac_target_device(amlp, mlp, mlp2, td)
+
+    def sac_target(self, actor, critic2, x_next, reward, gamma, alpha, clip_lo=-float('inf'), clip_hi=float('inf'), sample=True, seed=0, counter=0,
+                   row_offset=0, ls_lo=-20.0, ls_hi=2.0, terminal=None):
+        """x_next [B, Dx], reward [B], terminal [B] or None -> y [B], q_min [B], q1 [B], q2 [B] (None without critic2), next_action [B, A],
+        logp [B] (numpy)."""
+        self._loaded()
+        self._gaussian_actor(actor)
+        self._twin(critic2)
+        h = self._h
+        Dx, A = actor.widths[0], actor.widths[-1] // 2
+        x_next, reward = np.ascontiguousarray(x_next, np.float32), np.ascontiguousarray(reward, np.float32)
+        if x_next.ndim != 2 or x_next.shape[1] != Dx or reward.shape != (x_next.shape[0],):
+            raise ValueError('x_next %s must be [B, %d] and reward %s [B]' % (x_next.shape, Dx, reward.shape))
+        B = x_next.shape[0]
+        if terminal is not None:
+            terminal = np.ascontiguousarray(np.asarray(terminal) != 0, np.uint8)
+            if terminal.shape != (B,):
+                raise ValueError('terminal %s must be [B]' % (terminal.shape,))
+        y, qm, q1, na, lp = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32), np.empty((B, A), np.float32), np.empty(B, np.float32)
+        q2 = np.empty(B, np.float32) if critic2 is not None else None
+        if B == 0:
+            return y, qm, q1, q2, na, lp
+        ins = [x_next, reward] + ([terminal] if terminal is not None else [])
+        outs = [y, qm, q1, na, lp] + ([q2] if q2 is not None else [])
+        ptrs = []
+        try:
+            for arr in ins + outs:
+                ptrs.append(h.device_alloc(arr.nbytes))
+            for p, arr in zip(ptrs, ins):
+                h.upload(p, arr)
+            d_out = ptrs[len(ins):]
+            self.sac_target_device(actor, critic2, ptrs[0], ptrs[1], d_out[0], gamma, clip_lo, clip_hi, alpha, sample, seed, counter, row_offset, ls_lo, ls_hi,
+                                   d_terminal=ptrs[2] if terminal is not None else None, d_q_min=d_out[1], d_q1=d_out[2],
+                                   d_q2=d_out[5] if q2 is not None else None, d_next_action=d_out[3], d_logp=d_out[4], batch=B)
+            h.sync()
+            for arr, p in zip(outs, d_out):
+                h.download(arr, p)
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+        return y, qm, q1, q2, na, lp
 
     def close(self):
         """Free the uploaded network and the Adam states made for it."""

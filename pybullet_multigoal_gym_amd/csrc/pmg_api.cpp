@@ -1134,6 +1134,152 @@ int pmg_td3_target_device(pmg_env* e, const pmg_mlp* actor_target, const pmg_mlp
     return PMG_OK;
 }
 
+/* ---- SAC: the Gaussian head and the soft target ---- */
+/* a Gaussian actor has 2 A identity outputs; 0 or PMG_E_INVALID */
+static int gaussian_of(pmg_env* e, const PmgMlp& M, const char* who)
+{
+    if ((M.width[M.L] & 1) != 0 || M.out_act != 0)
+        return fail(e, PMG_E_INVALID, "%s: a Gaussian actor has an even number of outputs (means | log-stds) and out_activation 0, not %d outputs and out_activation %d",
+                    who, M.width[M.L], M.out_act);
+    return PMG_OK;
+}
+/* the clamp of the log-std; 0 or PMG_E_INVALID */
+static int sac_clamp_of(pmg_env* e, float lo, float hi, const char* who)
+{
+    if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi) return fail(e, PMG_E_INVALID, "%s: ls_lo %g / ls_hi %g must be finite and ordered", who, (double)lo, (double)hi);
+    return PMG_OK;
+}
+/* what both head entries check in their struct beyond the rows, and the head's launch arguments */
+static int sac_head_of(pmg_env* e, const pmg_sac_sample* s, int A, const char* who, PmgSac& G)
+{
+    if (!s) return fail(e, PMG_E_INVALID, "%s: the argument struct is null", who);
+    if (s->struct_size != (int32_t)sizeof(pmg_sac_sample)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, s->struct_size, sizeof(pmg_sac_sample));
+    if (int rc = sac_clamp_of(e, s->ls_lo, s->ls_hi, who)) return rc;
+    if (!s->d_action && !s->d_logp) return fail(e, PMG_E_INVALID, "%s: d_action and d_logp are both null: no output is requested", who);
+    if ((((size_t)s->d_action | (size_t)s->d_logp | (size_t)s->d_noise | (size_t)s->d_preact) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: an output is not aligned to 4 bytes", who);
+    if ((s->d_action && s->action_stride < A) || (s->d_noise && s->noise_stride < A) || (s->d_preact && s->preact_stride < 2 * A))
+        return fail(e, PMG_E_INVALID, "%s: strides %lld / %lld / %lld are smaller than the widths %d / %d / %d", who, (long long)s->action_stride,
+                    (long long)s->noise_stride, (long long)s->preact_stride, A, A, 2 * A);
+    memset(&G, 0, sizeof(G));
+    G.ls_lo = s->ls_lo; G.ls_hi = s->ls_hi; G.sample = s->sample != 0; G.seed = s->seed; G.counter = s->counter;
+    G.action = s->d_action; G.as = s->action_stride; G.logp = s->d_logp; G.noise = s->d_noise; G.ns = s->noise_stride;
+    G.preact = s->d_preact; G.ps = s->preact_stride;
+    return PMG_OK;
+}
+
+int pmg_sac_sample_device(pmg_env* e, const pmg_mlp* actor, const pmg_sac_sample* s)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_sac_sample_device";
+    PmgMlp M;
+    PmgSac G;
+    if (int rc = mlp_of(e, actor, who, M)) return rc;
+    if (int rc = gaussian_of(e, M, who)) return rc;
+    if (int rc = sac_head_of(e, s, M.width[M.L] / 2, who, G)) return rc;
+    if (!s->d_x) return fail(e, PMG_E_INVALID, "%s: d_x is null", who);
+    if (((size_t)s->d_x & 3) != 0) return fail(e, PMG_E_INVALID, "%s: d_x is not aligned to 4 bytes", who);
+    if (s->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)s->batch);
+    if (s->x_stride < M.width[0]) return fail(e, PMG_E_INVALID, "%s: x_stride %lld is smaller than the width %d", who, (long long)s->x_stride, M.width[0]);
+    if (s->row_offset < 0) return fail(e, PMG_E_INVALID, "%s: row_offset %lld is negative", who, (long long)s->row_offset);
+    if (s->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = s->batch;
+    G.row_offset = (unsigned long long)s->row_offset;
+    HIP_TRY(e, pmg_launch_sac_sample(M, G, s->d_x, s->x_stride, e->stream));
+    return PMG_OK;
+}
+
+int pmg_sac_act_env_device(pmg_env* e, const pmg_mlp* actor, int state_kind, const pmg_sac_sample* s)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_sac_act_env_device";
+    PmgMlp M;
+    PmgSac G;
+    if (int rc = mlp_of(e, actor, who, M)) return rc;
+    if (int rc = gaussian_of(e, M, who)) return rc;
+    const pmg_env::Norm* found = state_norm_of(e, state_kind, who); if (!found) return PMG_E_INVALID;
+    const pmg_env::Norm& ns = *found;
+    const pmg_env::Norm& ng = e->norm[PMG_NORM_GOAL];
+    const pmg_dims& d = e->dims;
+    if (M.width[0] != ns.D + ng.D || M.width[M.L] != 2 * d.action_dim)
+        return fail(e, PMG_E_INVALID, "%s: the network maps %d -> %d, the env needs %d + %d -> 2 * %d", who, M.width[0], M.width[M.L], ns.D, ng.D, d.action_dim);
+    if (int rc = sac_head_of(e, s, d.action_dim, who, G)) return rc;
+    if (!e->ever_reset) return fail(e, PMG_E_STATE, "%s: reset() must be called (for all envs) first", who);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    M.B = d.num_envs;
+    G.row_offset = (unsigned long long)e->cfg.env_index_offset;
+    PmgMlpEnv E;
+    E.rows = e->P.out;   /* the buffer of the LAST step, as pmg_device_ptr(PMG_BUF_PACKED) */
+    E.stride = d.packed_dim;
+    E.so = state_kind == PMG_NORM_OBSERVATION ? 0 : d.observation_dim;
+    E.dgo = d.observation_dim + d.policy_state_dim + d.goal_dim;
+    E.Ds = ns.D; E.Dg = ng.D; E.der_state = ns.der; E.der_goal = ng.der; E.cin = e->norm_clip_in; E.cout = e->norm_clip_out;
+    HIP_TRY(e, pmg_launch_sac_act(M, G, E, e->stream));
+    return PMG_OK;
+}
+
+int64_t pmg_sac_target_work_floats(const pmg_mlp* actor, int has_next_action, int64_t batch)
+{
+    if (!actor || actor->struct_size != (int32_t)sizeof(pmg_mlp) || actor->num_layers < 1 || actor->num_layers > 4) return -1;
+    if (batch < 0 || batch > ((int64_t)1 << 40)) return -1;
+    const int A2 = actor->width[actor->num_layers];
+    if (A2 < 2 || A2 > 256 || (A2 & 1) != 0) return -1;
+    return has_next_action ? 0 : batch * (A2 / 2);
+}
+
+int pmg_sac_target_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic1_target, const pmg_mlp* critic2_target, const pmg_sac_target* td)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_sac_target_device";
+    PmgMlp P, Q1, Q2;
+    if (int rc = mlp_of(e, actor, "pmg_sac_target_device (actor)", P)) return rc;
+    if (int rc = gaussian_of(e, P, "pmg_sac_target_device (actor)")) return rc;
+    if (int rc = mlp_of(e, critic1_target, "pmg_sac_target_device (critic 1)", Q1)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L] / 2;
+    if (int rc = critic_of(e, Q1, Dx + A, "pmg_sac_target_device (critic 1)")) return rc;
+    if (critic2_target) {
+        if (int rc = mlp_of(e, critic2_target, "pmg_sac_target_device (critic 2)", Q2)) return rc;
+        if (int rc = critic_of(e, Q2, Dx + A, "pmg_sac_target_device (critic 2)")) return rc;
+    } else
+        Q2 = Q1;
+    if (!td) return fail(e, PMG_E_INVALID, "%s: td is null", who);
+    if (td->struct_size != (int32_t)sizeof(pmg_sac_target)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, td->struct_size, sizeof(pmg_sac_target));
+    if (!td->d_x_next || !td->d_reward || !td->d_y) return fail(e, PMG_E_INVALID, "%s: d_x_next, d_reward or d_y is null", who);
+    if ((((size_t)td->d_x_next | (size_t)td->d_reward | (size_t)td->d_y | (size_t)td->d_q_min | (size_t)td->d_q1 | (size_t)td->d_q2 | (size_t)td->d_next_action |
+          (size_t)td->d_logp | (size_t)td->d_alpha | (size_t)td->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (td->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)td->batch);
+    if (td->x_stride < Dx) return fail(e, PMG_E_INVALID, "%s: x_stride %lld is smaller than the width %d", who, (long long)td->x_stride, Dx);
+    if (!(td->gamma >= 0.f) || std::isinf(td->gamma)) return fail(e, PMG_E_INVALID, "%s: gamma %g must be finite and >= 0", who, (double)td->gamma);
+    if (!(td->clip_lo <= td->clip_hi)) return fail(e, PMG_E_INVALID, "%s: clips %g / %g must be ordered and not NaN", who, (double)td->clip_lo, (double)td->clip_hi);
+    if (!(td->alpha >= 0.f) || std::isinf(td->alpha)) return fail(e, PMG_E_INVALID, "%s: alpha %g must be finite and >= 0", who, (double)td->alpha);
+    if (int rc = sac_clamp_of(e, td->ls_lo, td->ls_hi, who)) return rc;
+    if (td->row_offset < 0) return fail(e, PMG_E_INVALID, "%s: row_offset %lld is negative", who, (long long)td->row_offset);
+    const int64_t need = pmg_sac_target_work_floats(actor, td->d_next_action != nullptr, td->batch);
+    if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)td->batch);
+    if (need > 0 && (!td->d_work || td->work_floats < need))
+        return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld is below the %lld floats the action of the critics needs", who,
+                    (long long)td->work_floats, (long long)need);
+    if (td->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = Q1.B = Q2.B = td->batch;
+    PmgSacTd X;
+    memset(&X, 0, sizeof(X));
+    X.T.xn = td->d_x_next; X.T.xs = td->x_stride; X.T.reward = td->d_reward; X.T.term = td->d_terminal;
+    X.T.gamma = td->gamma; X.T.lo = td->clip_lo; X.T.hi = td->clip_hi;
+    X.T.y = td->d_y; X.T.qn = td->d_q_min;
+    X.q1 = td->d_q1; X.q2 = critic2_target ? td->d_q2 : nullptr;
+    X.twin = critic2_target != nullptr;
+    X.alpha = td->alpha; X.d_alpha = td->d_alpha;
+    X.G.ls_lo = td->ls_lo; X.G.ls_hi = td->ls_hi; X.G.sample = td->sample != 0; X.G.seed = td->seed; X.G.counter = td->counter;
+    X.G.row_offset = (unsigned long long)td->row_offset;
+    X.G.action = td->d_next_action ? td->d_next_action : td->d_work; X.G.as = A;
+    X.G.logp = td->d_logp;
+    HIP_TRY(e, pmg_launch_sac_target(P, Q1, Q2, X, e->stream));
+    return PMG_OK;
+}
+
 /* ---- back-propagation, Adam, Polyak ---- */
 int64_t pmg_mlp_grad_work_floats(const pmg_mlp* mlp, int64_t batch)
 {

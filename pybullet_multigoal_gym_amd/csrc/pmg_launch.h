@@ -94,6 +94,33 @@ struct PmgTd3 {
     unsigned long long key;                             /* mix(seed ^ mix(counter + GOLD)): set by the launcher */
 };
 hipError_t pmg_launch_td3_target(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgTd3& X, hipStream_t s);
+/* SAC's Gaussian head (pmg_sac_sample_device, pmg_sac_act_env_device, pmg_sac_target_device), validated by the caller.  The
+ * actor has width[L] = 2 A outputs: means | log standard deviations.  sample != 0: draws from (seed, counter), sample index
+ * (row_offset + row) * A + j (the env entry passes its env_index_offset as row_offset).  action / noise [B, A] at as / ns floats, preact
+ * [B, 2 A] at ps, logp [B]: any may be null. */
+struct PmgSac {
+    float ls_lo, ls_hi;
+    int sample;
+    unsigned long long seed, counter, row_offset;
+    unsigned long long key;                             /* mix(seed ^ mix(counter + GOLD)): set by the launcher */
+    float* action; long long as;
+    float* logp;
+    float* noise; long long ns;
+    float* preact; long long ps;
+};
+hipError_t pmg_launch_sac_sample(const PmgMlp& M, const PmgSac& G, const float* d_in, long long in_stride, hipStream_t s);
+hipError_t pmg_launch_sac_act(const PmgMlp& M, const PmgSac& G, const PmgMlpEnv& E, hipStream_t s);
+/* SAC's soft target (pmg_sac_target_device), validated by the caller.  T as for pmg_launch_td3_target.  G: the head's arguments; G.action =
+ * where a' [B, A] is written and read back for every critic (the caller's d_next_action, else the workspace; never null), G.as = A; G.noise
+ * and G.preact are null.  d_alpha: a device scalar that replaces alpha when not null.  critic2 is read only when twin != 0. */
+struct PmgSacTd {
+    PmgTd T;
+    PmgSac G;
+    float* q1; float* q2;
+    int twin;
+    float alpha; const float* d_alpha;
+};
+hipError_t pmg_launch_sac_target(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgSacTd& X, hipStream_t s);
 
 /* back-propagation, Adam and Polyak (pmg_mlp_grad_device, pmg_mlp_adam_device, pmg_mlp_polyak_device), validated by the caller.
  * Rows x[r] | a[r] as pmg_launch_mlp_q takes them (a == null: raw rows of x_dim = width[0] floats).  dw / db: the gradient tensors, used iff

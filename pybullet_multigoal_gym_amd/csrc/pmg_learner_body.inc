@@ -755,6 +755,153 @@ __global__ void __launch_bounds__(256) pmg_k_td3_target(PmgMlp P, PmgMlp Q1, Pmg
         __syncthreads();                                             /* the next tile's rows overwrite this one's */
     }
 }
+/* SAC's Gaussian head (include/pmg.h, DESIGN.md 3.15): the ONE definition of (mean, raw log-std, sample index) -> action a = tanh(u), the
+ * noise n used and the summand l of log pi, for pmg_k_sac and pmg_k_sac_target, which thereby agree bit for bit.  The draws are
+ * td3_noise's; every multiply-add is an fmaf, so the build contracts nothing.  log(1 - tanh^2 u) is taken as 2 (log 2 - u - softplus(-2 u)):
+ * no cancellation where |a| rounds to 1. */
+struct SacHead { float a, n, l; };
+__device__ __forceinline__ SacHead sac_head(const PmgSac& G, float m, float ls_raw, unsigned long long s)
+{
+    const float ls = fminf(fmaxf(ls_raw, G.ls_lo), G.ls_hi);
+    float n = 0.f;
+    if (G.sample) {
+        const unsigned long long zb = G.key + (4ull * s + 1ull) * HER_GOLD;
+        const unsigned int r0 = (unsigned int)(her_mix(zb) >> 32), r1 = (unsigned int)(her_mix(zb + HER_GOLD) >> 32);
+        const float u1 = (float)((r0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r1 >> 8) * 0x1p-24f;
+        n = sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    }
+    const float sd = expf(ls), u = fmaf(sd, n, m);
+    const float w = -2.f * u, sp = fmaxf(w, 0.f) + log1pf(expf(-fabsf(w)));
+    const float c2 = (0.69314718055994530942f - u) - sp;
+    SacHead h;
+    h.a = tanhf(u);
+    h.n = n;
+    h.l = fmaf(-2.f, c2, fmaf(-0.5f * n, n, -ls) - 0.91893853320467274178f);
+    return h;
+}
+/* log pi of row r of the tile, whose columns [0, A) hold the summands: ONE chain from +0.0, j ascending, by the row's thread */
+__device__ __forceinline__ float sac_logp(const float* tile, int r, int A)
+{
+    float acc = 0.f;
+    for (int j = 0; j < A; j++) acc = acc + tile[r * MLP_LD + j];
+    return acc;
+}
+/* Action, log-probability and noise of a Gaussian actor (pmg_sac_sample_device, pmg_sac_act_env_device), pmg_k_mlp's sibling: gather, the
+ * layers, then the head.  The tile holds z: means in columns [0, A), raw log-stds in [A, 2 A).  The thread of (row, unit j < A) in
+ * pmg_k_mlp's map reads columns j and A + j of its row, writes the outputs and puts l_j back into column j.  No other thread reads or
+ * writes these two columns in the pass (another unit j' of the row touches j' and A + j', and j' != j, A + j' != j as j < A), so the pass
+ * needs no barrier inside; the one behind it orders the l_j before the sum of the row's thread, and the closing one that sum before the
+ * next tile's gather.  Rows past the batch are left alone: nothing reads them. */
+template <class Src>
+__global__ void __launch_bounds__(256) pmg_k_sac(Src S, PmgMlp M, PmgSac G)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int A = M.width[M.L] >> 1;
+    const long long ntiles = (M.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, M.B, M.width[0], (M.width[0] + 1) & ~1, t);
+        __syncthreads();
+        mlp_layers(tile, M, lane, wave, col);
+        for (int i = t; i < MLP_ROWS * A; i += 256) {
+            const int r = i / A, j = i - r * A;
+            const long long row = row0 + r;
+            if (row >= M.B) break;
+            const float m = tile[r * MLP_LD + j], ls = tile[r * MLP_LD + A + j];
+            const SacHead h = sac_head(G, m, ls, (G.row_offset + (unsigned long long)row) * (unsigned long long)A + (unsigned long long)j);
+            if (G.preact) { G.preact[row * G.ps + j] = m; G.preact[row * G.ps + A + j] = ls; }
+            if (G.action) G.action[row * G.as + j] = h.a;
+            if (G.noise) G.noise[row * G.ns + j] = h.n;
+            tile[r * MLP_LD + j] = h.l;
+        }
+        __syncthreads();                                             /* every l_j of the tile is written */
+        if (G.logp && t < MLP_ROWS && row0 + t < M.B) G.logp[row0 + t] = sac_logp(tile, t, A);
+        __syncthreads();                                             /* the next tile's rows overwrite this one's */
+    }
+}
+/* SAC's soft target (pmg_sac_target_device, DESIGN.md 3.15), pmg_k_td3_target's sibling on the same tile:
+ * y = clip(r + gamma (min(Q1, Q2)(x', a') - alpha log pi(a' | x'))), a' and log pi from the head above.
+ * Hand-over.  The actor leaves 2 A columns, so the descending eight-unit schedule of the siblings does not carry over: with Dx < A a pass
+ * would store an action into a column a later pass still reads as a log-std.  Instead NOTHING is handed over through the tile: the thread
+ * of (row, unit) in pmg_k_sac's map writes a' to G.action (the caller's d_next_action, or the workspace) and l_j into its own column j --
+ * the only thread that touches columns j and A + j of that row in the pass.  Barrier; the row's thread (t < 32) sums log pi into a
+ * register; barrier (the sums are read: the tile is free).  Then the row x' | a' is built for critic 1 exactly as pmg_k_td3_target builds
+ * it for critic 2: x' from memory, a' from G.action by the SAME (row, unit) -> thread map, so a thread reads only its own earlier store
+ * and no ordering between threads is involved.  The same rebuild runs again in front of critic 2.
+ * Stale tile: when a rebuild starts, the tile holds the actor's or critic 1's activations (which may be inf) in columns up to the widest
+ * layer.  The regather writes columns [0, Dx) of all 32 rows, the rebuild's pass columns [Dx, Dx + A) of all 32 rows, thread t < 32 column
+ * Dx + A of an odd Dx + A; rows past the batch receive +0.0 in each.  These are all the columns a critic's layer 0 reads, so no stale
+ * activation meets a weight or a stand-in zero.  Nothing in a rebuild READS the tile, so it needs no barrier inside. */
+__device__ __forceinline__ void sac_rebuild(float* tile, const MlpRawRows& S, const float* keep, long long row0, long long B, int Dx, int A, int t)
+{
+    mlp_gather(tile, S, row0, B, Dx, Dx, t);
+    for (int i = t; i < MLP_ROWS * A; i += 256) {                    /* the head's map: a thread reads what it stored itself */
+        const int r = i / A, j = i - r * A;
+        tile[r * MLP_LD + Dx + j] = row0 + r < B ? keep[(row0 + r) * A + j] : 0.f;
+    }
+    if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+}
+__global__ void __launch_bounds__(256) pmg_k_sac_target(PmgMlp P, PmgMlp Q1, PmgMlp Q2, PmgSacTd X)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L] >> 1;
+    const MlpRawRows S = {X.T.xn, X.T.xs};
+    float* keep = X.G.action;
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        mlp_layers(tile, P, lane, wave, col);
+        for (int i = t; i < MLP_ROWS * A; i += 256) {
+            const int r = i / A, j = i - r * A;
+            const long long row = row0 + r;
+            if (row >= P.B) break;
+            const SacHead h = sac_head(X.G, tile[r * MLP_LD + j], tile[r * MLP_LD + A + j],
+                                       (X.G.row_offset + (unsigned long long)row) * (unsigned long long)A + (unsigned long long)j);
+            keep[row * A + j] = h.a;
+            tile[r * MLP_LD + j] = h.l;
+        }
+        __syncthreads();                                             /* every l_j of the tile is written */
+        const bool own = t < MLP_ROWS && row0 + t < P.B;             /* this thread forms the outputs of row row0 + t */
+        float logp = 0.f;
+        if (own) {
+            logp = sac_logp(tile, t, A);
+            if (X.G.logp) X.G.logp[row0 + t] = logp;
+        }
+        __syncthreads();                                             /* the sums are read: the tile is free */
+        sac_rebuild(tile, S, keep, row0, P.B, Dx, A, t);
+        __syncthreads();
+        mlp_layers(tile, Q1, lane, wave, col);
+        float q = 0.f;
+        if (own) {
+            const float z = tile[t * MLP_LD];
+            q = Q1.out_act ? tanhf(z) : z;
+            if (X.q1) X.q1[row0 + t] = q;
+        }
+        if (X.twin) {
+            __syncthreads();                                         /* q1 is read: column 0 is free */
+            sac_rebuild(tile, S, keep, row0, P.B, Dx, A, t);
+            __syncthreads();
+            mlp_layers(tile, Q2, lane, wave, col);
+            if (own) {
+                const float z = tile[t * MLP_LD], q2 = Q2.out_act ? tanhf(z) : z;
+                if (X.q2) X.q2[row0 + t] = q2;
+                q = fminf(q, q2);
+            }
+        }
+        if (own) {
+            const float alpha = X.d_alpha ? *X.d_alpha : X.alpha;
+            const float rw = X.T.reward[row0 + t];
+            const float v = X.T.term && X.T.term[row0 + t] ? rw : fmaf(X.T.gamma, fmaf(-alpha, logp, q), rw);
+            X.T.y[row0 + t] = fminf(fmaxf(v, X.T.lo), X.T.hi);
+            if (X.T.qn) X.T.qn[row0 + t] = q;
+        }
+        __syncthreads();                                             /* the next tile's rows overwrite this one's */
+    }
+}
 static unsigned mlp_grid(long long B)
 {
     const long long want = (B + MLP_ROWS - 1) / MLP_ROWS;
@@ -795,6 +942,32 @@ hipError_t pmg_launch_td3_target(const PmgMlp& actor, const PmgMlp& critic1, con
     PmgTd3 X = T;
     X.key = her_mix(X.seed ^ her_mix(X.counter + HER_GOLD));
     hipLaunchKernelGGL(pmg_k_td3_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic1, critic2, X);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_sac_sample(const PmgMlp& M, const PmgSac& head, const float* d_in, long long in_stride, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    PmgSac G = head;
+    G.key = her_mix(G.seed ^ her_mix(G.counter + HER_GOLD));
+    const MlpRawRows S = {d_in, in_stride};
+    hipLaunchKernelGGL((pmg_k_sac<MlpRawRows>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M, G);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_sac_act(const PmgMlp& M, const PmgSac& head, const PmgMlpEnv& E, hipStream_t s)
+{
+    if (M.B <= 0) return hipSuccess;
+    PmgSac G = head;
+    G.key = her_mix(G.seed ^ her_mix(G.counter + HER_GOLD));
+    const MlpEnvRows S = {E};
+    hipLaunchKernelGGL((pmg_k_sac<MlpEnvRows>), dim3(mlp_grid(M.B)), dim3(256), 0, s, S, M, G);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_sac_target(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgSacTd& T, hipStream_t s)
+{
+    if (actor.B <= 0) return hipSuccess;
+    PmgSacTd X = T;
+    X.G.key = her_mix(X.G.seed ^ her_mix(X.G.counter + HER_GOLD));
+    hipLaunchKernelGGL(pmg_k_sac_target, dim3(mlp_grid(actor.B)), dim3(256), 0, s, actor, critic1, critic2, X);
     return hipGetLastError();
 }
 

@@ -295,6 +295,15 @@ class KukaVecEnv:
         return self._actor
 
     @property
+    def gaussian_actor(self):
+        """The stochastic (tanh-squashed Gaussian) actor of a SAC learner on the device (sac.GaussianActor): sampled actions with their
+        log-probabilities on minibatch rows and on the env's current rows, created on first use."""
+        if getattr(self, '_gaussian_actor', None) is None:
+            from .sac import GaussianActor
+            self._gaussian_actor = GaussianActor(self)
+        return self._gaussian_actor
+
+    @property
     def critic(self):
         """The critic network of this env's learner on the device (critic.Critic): Q(x, a) and fused TD targets, created on first
         access."""
@@ -307,6 +316,8 @@ class KukaVecEnv:
         if not self._closed:
             if getattr(self, '_actor', None) is not None:
                 self._actor.close()
+            if getattr(self, '_gaussian_actor', None) is not None:
+                self._gaussian_actor.close()
             if getattr(self, '_critic', None) is not None:
                 self._critic.close()
             self.handle.close()
