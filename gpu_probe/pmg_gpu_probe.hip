@@ -29,6 +29,29 @@
 #undef PRIM_FN
 #undef PRIM_WR
 
+#define WV wv
+#define NSP pmg
+#define LEAN_FN lean_probe_wv
+#define FK_FN fk_probe_wv
+#define IK_FN ik_probe_wv
+#include "pmg_lean_probe.inc"
+#undef WV
+#undef NSP
+#undef LEAN_FN
+#undef FK_FN
+#undef IK_FN
+#define WV wr
+#define NSP pmgp
+#define LEAN_FN lean_probe_wr
+#define FK_FN fk_probe_wr
+#define IK_FN ik_probe_wr
+#include "pmg_lean_probe.inc"
+#undef WV
+#undef NSP
+#undef LEAN_FN
+#undef FK_FN
+#undef IK_FN
+
 namespace {
 
 /* device buffers of one call: freed on every path */
@@ -168,6 +191,24 @@ __global__ void __launch_bounds__(64) k_ik_packed(int n, const float* q, const f
         const float r = ik_solve(c, l < NJ ? q[9 * cs + l] : 0.f, target + 3 * cs);
         if (valid && l < NJ) q_out[9 * cs + l] = r;
     }
+}
+
+/* ---- PMG_IK_LEAN: the lean primitives, fk() in float32 and ik_solve() in either layout (pmg_lean_probe.inc) ---------------- */
+template <bool WR>
+__global__ void __launch_bounds__(64) k_lean_prim(int fam, const float* in, float* out)
+{
+    if (WR) lean_probe_wr(fam, in, out);
+    else lean_probe_wv(fam, in, out);
+}
+__global__ void __launch_bounds__(64) k_fk32(int n, const float* q, float* out)
+{
+    __shared__ pmg::LaneTabStore lcs;
+    fk_probe_wv(lcs, n, q, out);
+}
+__global__ void __launch_bounds__(64) k_fk32_packed(int n, const float* q, float* out)
+{
+    __shared__ pmgp::LaneTabStore lcs;
+    fk_probe_wr(lcs, n, q, out);
 }
 
 /* ---- narrowphase: one pair per lane, every operand in LDS as in the product (tools/prof_narrow.hip's layout) ---------- */
@@ -384,6 +425,37 @@ int pmgd_ik(int packed, int n, const float* q, const float* target, float* q_out
     }
     d.sync();
     d.down(q_out, dout, 9 * (size_t)n);
+    return (int)d.err;
+}
+/* PMG_IK_LEAN of this build, and the probes of pmg_lean_probe.inc: in [NIN][64] -> out [NOUT][64] (in and out, as pmgd_prim) */
+int pmgd_ik_lean() { return PMG_IK_LEAN; }
+int pmgd_lean_prim(int wr_ns, int fam, const float* in, float* out)
+{
+    if (fam < 0 || fam >= prim::LEAN_FAMILIES) return -1;
+    Dev d;
+    const float* din = d.up(in, (size_t)prim::NIN * 64);
+    float* dout = d.up(out, (size_t)prim::NOUT * 64);
+    if (d.err == hipSuccess) {
+        if (wr_ns) hipLaunchKernelGGL(k_lean_prim<true>, dim3(1), dim3(64), 0, 0, fam, din, dout);
+        else hipLaunchKernelGGL(k_lean_prim<false>, dim3(1), dim3(64), 0, 0, fam, din, dout);
+    }
+    d.sync();
+    d.down(out, dout, (size_t)prim::NOUT * 64);
+    return (int)d.err;
+}
+/* fk() in float32: q [n][9] -> out [n][16][18] (R, p, S of the sixteen lanes of the env's row) */
+int pmgd_fk(int packed, int n, const float* q, float* out)
+{
+    if (n < 1 || n > 4096) return -1;
+    Dev d;
+    const float* dq = d.up(q, 9 * (size_t)n);
+    float* dout = d.up<float>(nullptr, 16 * prim::FK_ROW_FLOATS * (size_t)n);
+    if (d.err == hipSuccess) {
+        if (packed) hipLaunchKernelGGL(k_fk32_packed, dim3(1), dim3(64), 0, 0, n, dq, dout);
+        else hipLaunchKernelGGL(k_fk32, dim3(1), dim3(64), 0, 0, n, dq, dout);
+    }
+    d.sync();
+    d.down(out, dout, 16 * prim::FK_ROW_FLOATS * (size_t)n);
     return (int)d.err;
 }
 

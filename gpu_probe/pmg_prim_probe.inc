@@ -114,6 +114,61 @@ extern "C" int pmge_mfma(int n, int steps, const float* a, const float* b, const
     emu::launch(1, 64, [&]() { prim::mfma_chain(n, steps, a, b, c, out); });
     return 0;
 }
+/* the lean primitives, fk() in float32 and ik_solve() in either layout (PMG_IK_LEAN): pmgd_lean_prim / pmgd_fk / pmgd_ik of the device
+ * probe library on the emulator.  pmg_lean_probe.inc once per layout, whatever layout the includer of THIS file is at */
+#pragma push_macro("WV")
+#undef WV
+#define WV wv
+#define NSP pmg
+#define LEAN_FN lean_probe_wv
+#define FK_FN fk_probe_wv
+#define IK_FN ik_probe_wv
+#include "pmg_lean_probe.inc"
+#undef WV
+#undef NSP
+#undef LEAN_FN
+#undef FK_FN
+#undef IK_FN
+#define WV wr
+#define NSP pmgp
+#define LEAN_FN lean_probe_wr
+#define FK_FN fk_probe_wr
+#define IK_FN ik_probe_wr
+#include "pmg_lean_probe.inc"
+#undef WV
+#undef NSP
+#undef LEAN_FN
+#undef FK_FN
+#undef IK_FN
+#pragma pop_macro("WV")
+extern "C" int pmge_ik_lean() { return PMG_IK_LEAN; }
+extern "C" int pmge_lean_prim(int wr_ns, int fam, const float* in, float* out)
+{
+    if (fam < 0 || fam >= prim::LEAN_FAMILIES) return -1;
+    emu::launch(1, 64, [&]() {
+        if (wr_ns) lean_probe_wr(fam, in, out);
+        else lean_probe_wv(fam, in, out);
+    });
+    return 0;
+}
+extern "C" int pmge_fk(int packed, int n, const float* q, float* out)
+{
+    if (n < 1 || n > 4096) return -1;
+    emu::launch(1, 64, [&]() {
+        if (packed) { __shared__ pmgp::LaneTabStore lcs; fk_probe_wr(lcs, n, q, out); }
+        else { __shared__ pmg::LaneTabStore lcs; fk_probe_wv(lcs, n, q, out); }
+    });
+    return 0;
+}
+extern "C" int pmge_ik(int packed, int n, const float* q, const float* target, float* q_out)
+{
+    if (n < 1 || n > 4096) return -1;
+    emu::launch(1, 64, [&]() {
+        if (packed) { __shared__ pmgp::LaneTabStore lcs; ik_probe_wr(lcs, n, q, target, q_out); }
+        else { __shared__ pmg::LaneTabStore lcs; ik_probe_wv(lcs, n, q, target, q_out); }
+    });
+    return 0;
+}
 #endif
 #endif
 

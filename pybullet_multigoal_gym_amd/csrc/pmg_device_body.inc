@@ -15,9 +15,14 @@ __device__ __forceinline__ void flush(long long* out) { __syncthreads(); if (blo
 #define PMG_STAMP(var, i) do { long long t_ = prof::now(); if (threadIdx.x == 0 && blockIdx.x == 0) prof::acc()[i] += t_ - var; var = prof::now(); } while (0)
 #define PMG_IK_T0() long long ik_t_ = prof::now()
 #define PMG_IK_T(i) PMG_STAMP(ik_t_, i)
+/* a stamp behind the values v[0 .. n) of the phase it closes: each passes through an empty asm, which keeps the IR from moving their
+ * computation past the stamp.  It does NOT pin the clock read in the machine schedule: the four IK phases still sum to 40-55 % of an
+ * iteration (profiles/r09_ik_ab.txt §2), so the IK is measured as a whole -- slot 5 over slot 31 -- and the phases only hint */
+#define PMG_IK_TV(i, v, n) do { _Pragma("unroll") for (int pin_ = 0; pin_ < (n); pin_++) asm volatile("" : "+v"((v)[pin_])); PMG_STAMP(ik_t_, i); } while (0)
 #else
 #define PMG_IK_T0() do { } while (0)
 #define PMG_IK_T(i) do { } while (0)
+#define PMG_IK_TV(i, v, n) do { } while (0)
 #endif
 constexpr int NJ = 9;
 constexpr float DT = 0.002f;            /* base_env.py:217-219 */
@@ -259,6 +264,9 @@ struct Kin {
 template <int S>
 __device__ __forceinline__ void fk_scan_level(float* R, float* p)
 {
+#if PMG_IK_LEAN
+    WV::template affine_shr<S>(R, p);
+#else
     float A[9], a3[3];
 #pragma unroll
     for (int a = 0; a < 9; a++) A[a] = WV::row_shr<S>(R[a], (a % 4 == 0) ? 1.f : 0.f);
@@ -268,6 +276,7 @@ __device__ __forceinline__ void fk_scan_level(float* R, float* p)
     mat3v(A, p, t);
     p[0] = a3[0] + t[0]; p[1] = a3[1] + t[1]; p[2] = a3[2] + t[2];
     mat3m(A, R, R);
+#endif
 }
 
 /* forward kinematics of the chain; lanes >= 9 end up holding link 7's frame (lane 6's) */
@@ -439,7 +448,7 @@ __device__ __forceinline__ float ik_solve(const LaneConst& c, float q, const flo
         fk_scan_level<1>(R, p);
         fk_scan_level<2>(R, p);
         fk_scan_level<4>(R, p);
-        PMG_IK_T(27);
+        PMG_IK_TV(27, R, 9);
         float tip[3], Rt[9];
         {
             float t[12], o[12];
@@ -467,7 +476,7 @@ __device__ __forceinline__ float ik_solve(const LaneConst& c, float q, const flo
         if (ang > 3.14159265358979f) ang -= 6.28318530717959f;
         float sc = vn > 1e-12f ? ang / vn : 0.f;
         e[3] = dx * sc; e[4] = dy * sc; e[5] = dz * sc;
-        PMG_IK_T(28);
+        PMG_IK_TV(28, e, 6);
         /* Jacobian column of this lane's joint: [z x (tip - p); z], z = the joint axis = third column of the link frame */
         float col[6] = {0, 0, 0, 0, 0, 0};
         if (arm) {
@@ -480,11 +489,19 @@ __device__ __forceinline__ float ik_solve(const LaneConst& c, float q, const flo
         float row[6], rhs;
         {
             float A[6][6];
+#if PMG_IK_LEAN
+            float g[21];
+            WV::half_gram6(col, g);
+#endif
 #pragma unroll
             for (int a = 0; a < 6; a++)
 #pragma unroll
                 for (int b = a; b < 6; b++) {
+#if PMG_IK_LEAN
+                    float s = g[(a * (13 - a)) / 2 + b - a];
+#else
                     float s = WV::row_sum(col[a] * col[b]);
+#endif
                     if (a == b) s += IK_DAMPING;
                     A[a][b] = s;
                     A[b][a] = s;
@@ -501,14 +518,18 @@ __device__ __forceinline__ float ik_solve(const LaneConst& c, float q, const flo
             for (int a = 4; a >= 0; a--) v = l == a ? e[a] : v;
             rhs = v;
         }
-        PMG_IK_T(29);
+        PMG_IK_TV(29, row, 6);
         ik_pivot<0>(row, rhs, l); ik_pivot<1>(row, rhs, l); ik_pivot<2>(row, rhs, l);
         ik_pivot<3>(row, rhs, l); ik_pivot<4>(row, rhs, l); ik_pivot<5>(row, rhs, l);
         float dq = WV::dot6_lanes_r0(col, rhs);      /* J^T y: y_a sits in lane a */
+#if PMG_IK_LEAN
+        float mx = WV::half_max(fabsf(dq));          /* (dq is an exact zero beyond the arm: lanes 7..15) */
+#else
         float mx = WV::row_max(fabsf(dq));
+#endif
         if (mx > IK_MAX_STEP) dq *= IK_MAX_STEP / mx;
         qa += dq;
-        PMG_IK_T(30);
+        PMG_IK_TV(30, &qa, 1);
 #ifdef PMG_PROFILE
         if (threadIdx.x == 0 && blockIdx.x == 0) prof::acc()[31] += 1;
 #endif

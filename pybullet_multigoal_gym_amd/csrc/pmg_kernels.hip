@@ -300,4 +300,6 @@ hipError_t pmg_launch_reset(const pmg::EnvParams& P, const unsigned char* d_mask
 /* the setting of PMG_ROWSETUP_PIPELINE the kernels above were built with: A/B builds and the tests that compare the two settings
  * tell their libraries apart by it (a build diagnostic, not part of include/pmg.h) */
 extern "C" int pmg_rowsetup_pipeline(void) { return PMG_ROWSETUP_PIPELINE; }
+/* ... and the setting of PMG_IK_LEAN (pmg_wave.h, pmg_device_body.inc: ik_solve and the scan of fk) */
+extern "C" int pmg_ik_lean(void) { return PMG_IK_LEAN; }
 #include "pmg_learner_body.inc"   /* the learner side: rewards, running normaliser, policy-input rows, HER minibatches */

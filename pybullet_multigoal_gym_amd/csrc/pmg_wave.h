@@ -656,3 +656,150 @@ inline acc16 mfma_32x32x2(float a, float b, acc16 c)
 #endif
 }  // namespace wv
 #endif
+
+/* ---- the lean forms of the IK iteration and the FK scan (PMG_IK_LEAN, pmg_device_body.inc) -------------------------------
+ * Outside the guard for the reason given above: each primitive has its device form and its emulator branch side by side.
+ * Three primitives; each is the arithmetic the compiler made of the C++ it replaces, operation for operation, with the
+ * moves that only carried operands about taken out.  fl() = one float32 rounding, fma(a, b, c) = fl(a b + c).
+ *
+ * affine_shr<S>(R, p): one level of the scan of affine maps along a 16-lane row, (R, p) <- (A, a) o (R, p) with (A, a) the
+ *   map of lane i - S of the row and the IDENTITY where the row has no such lane:
+ *     R'[3 i + j] = fma(A[3 i + 2], R[6 + j], fma(A[3 i], R[j], fl(A[3 i + 1] R[3 + j])))
+ *     p'[i]       = fl(a[i] + fma(A[3 i + 2], p[2], fma(A[3 i], p[0], fl(A[3 i + 1] p[1]))))
+ *   -- the middle product rounded, the outer two fused onto it: what hipcc's contraction makes of `x y + z w + u v`
+ *   (mat3m / mat3v).  The six off-diagonal entries of A and a ride on the DPP port of the multiply-adds that use them,
+ *   zero-filled (bound_ctrl); the three diagonal ones, whose identity value is 1, are fetched with a fill as before.
+ *   (Emulator: g++ contracts nothing -- the same tree with every product rounded, which is its fk_scan_level.)
+ * half_gram6(x, s): s[k] = sum over the 8-lane half row of x[a] x[b], k = (a, b) with a <= b < 6 in row-major order, in every
+ *   lane i of the half row:  t_i = fma(x_i[a], x_i[b], fl(x_(i^1)[a] x_(i^1)[b]));  u_i = fl(t_i + t_(i^2));  s = fl(u_i + u_(7 - i))
+ *   -- row_sum(x[a] * x[b]) as compiled (the lane's own product fused onto its neighbour's rounded one), without the
+ *   row_mirror step.  Lanes of one half row do NOT all hold the same bits: level 1 is not symmetric.
+ *   (Emulator: half_sum of the rounded products.)
+ * half_max(v): fmaxf over the 8-lane half row, in every lane of it (a NaN lane is passed over). */
+#ifndef PMG_WAVE_LEAN_H
+#define PMG_WAVE_LEAN_H
+#ifndef PMG_IK_LEAN
+#define PMG_IK_LEAN 1
+#endif
+namespace wv {
+#ifndef PMG_EMULATE
+/* lane <- its DPP source, 0 where the control names none */
+template <int CTRL>
+__device__ __forceinline__ float dpp0(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
+template <int S>
+__device__ __forceinline__ void affine_shr(float* R, float* p)
+{
+    const float d0 = row_shr<S>(R[0], 1.f), d1 = row_shr<S>(R[4], 1.f), d2 = row_shr<S>(R[8], 1.f);
+    float n[12];
+#if !defined(PMG_NO_R0_DPP) && !defined(PMG_NO_DPP_FMAC)
+    /* %0-8 R', %9-11 p'; %12-20 R, %21-23 p, %24-26 the shifted diagonal, %27 S.  Every DPP source is an INPUT of the block:
+     * the one s_nop in front covers all of them */
+#define PMG_SHRZ " row_shr:%27 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+    asm("s_nop 1\n\t"
+        "v_mul_f32_dpp %0, %13, %15" PMG_SHRZ "v_mul_f32_dpp %1, %13, %16" PMG_SHRZ "v_mul_f32_dpp %2, %13, %17" PMG_SHRZ
+        "v_mul_f32_e32 %3, %25, %15\n\t" "v_mul_f32_e32 %4, %25, %16\n\t" "v_mul_f32_e32 %5, %25, %17\n\t"
+        "v_mul_f32_dpp %6, %19, %15" PMG_SHRZ "v_mul_f32_dpp %7, %19, %16" PMG_SHRZ "v_mul_f32_dpp %8, %19, %17" PMG_SHRZ
+        "v_mul_f32_dpp %9, %13, %22" PMG_SHRZ "v_mul_f32_e32 %10, %25, %22\n\t" "v_mul_f32_dpp %11, %19, %22" PMG_SHRZ
+        "v_fmac_f32_e32 %0, %24, %12\n\t" "v_fmac_f32_e32 %1, %24, %13\n\t" "v_fmac_f32_e32 %2, %24, %14\n\t"
+        "v_fmac_f32_dpp %3, %15, %12" PMG_SHRZ "v_fmac_f32_dpp %4, %15, %13" PMG_SHRZ "v_fmac_f32_dpp %5, %15, %14" PMG_SHRZ
+        "v_fmac_f32_dpp %6, %18, %12" PMG_SHRZ "v_fmac_f32_dpp %7, %18, %13" PMG_SHRZ "v_fmac_f32_dpp %8, %18, %14" PMG_SHRZ
+        "v_fmac_f32_e32 %9, %24, %21\n\t" "v_fmac_f32_dpp %10, %15, %21" PMG_SHRZ "v_fmac_f32_dpp %11, %18, %21" PMG_SHRZ
+        "v_fmac_f32_dpp %0, %14, %18" PMG_SHRZ "v_fmac_f32_dpp %1, %14, %19" PMG_SHRZ "v_fmac_f32_dpp %2, %14, %20" PMG_SHRZ
+        "v_fmac_f32_dpp %3, %17, %18" PMG_SHRZ "v_fmac_f32_dpp %4, %17, %19" PMG_SHRZ "v_fmac_f32_dpp %5, %17, %20" PMG_SHRZ
+        "v_fmac_f32_e32 %6, %26, %18\n\t" "v_fmac_f32_e32 %7, %26, %19\n\t" "v_fmac_f32_e32 %8, %26, %20\n\t"
+        "v_fmac_f32_dpp %9, %14, %23" PMG_SHRZ "v_fmac_f32_dpp %10, %17, %23" PMG_SHRZ "v_fmac_f32_e32 %11, %26, %23\n\t"
+        "v_add_f32_dpp %9, %21, %9" PMG_SHRZ "v_add_f32_dpp %10, %22, %10" PMG_SHRZ
+        "v_add_f32_dpp %11, %23, %11 row_shr:%27 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+        : "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3]), "=&v"(n[4]), "=&v"(n[5]), "=&v"(n[6]), "=&v"(n[7]), "=&v"(n[8]), "=&v"(n[9]), "=&v"(n[10]),
+          "=&v"(n[11])
+        : "v"(R[0]), "v"(R[1]), "v"(R[2]), "v"(R[3]), "v"(R[4]), "v"(R[5]), "v"(R[6]), "v"(R[7]), "v"(R[8]), "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(d0), "v"(d1),
+          "v"(d2), "n"(S));
+#undef PMG_SHRZ
+#else
+    const float d[3] = {d0, d1, d2};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const float a0 = i == 0 ? d[0] : dpp0<0x110 + S>(R[3 * i]), a1 = i == 1 ? d[1] : dpp0<0x110 + S>(R[3 * i + 1]), a2 = i == 2 ? d[2] : dpp0<0x110 + S>(R[3 * i + 2]);
+#pragma unroll
+        for (int j = 0; j < 3; j++) n[3 * i + j] = __builtin_fmaf(a2, R[6 + j], __builtin_fmaf(a0, R[j], a1 * R[3 + j]));
+        n[9 + i] = dpp0<0x110 + S>(p[i]) + __builtin_fmaf(a2, p[2], __builtin_fmaf(a0, p[0], a1 * p[1]));
+    }
+#endif
+#pragma unroll
+    for (int a = 0; a < 9; a++) R[a] = n[a];
+#pragma unroll
+    for (int a = 0; a < 3; a++) p[a] = n[9 + a];
+}
+/* (plain C++ in every build: the compiler folds the two adds into v_add_f32_dpp itself and pads its own hazards) */
+__device__ __forceinline__ void half_gram6(const float* x, float* s)
+{
+    float q[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) q[a] = dpp0<0xB1>(x[a]);   /* quad_perm [1,0,3,2]: the neighbour's column */
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = a; b < 6; b++) {
+            float t = __builtin_fmaf(x[a], x[b], q[a] * q[b]);
+            t += dpp0<0x4E>(t);   /* quad_perm [2,3,0,1] */
+            t += dpp0<0x141>(t);  /* row_half_mirror */
+            s[k++] = t;
+        }
+}
+__device__ __forceinline__ float half_max(float v)
+{
+#if !defined(PMG_NO_R0_DPP) && !defined(PMG_NO_DPP_FMAC)
+    asm("s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf"
+        : "+v"(v));
+#else
+    v = fmaxf(v, dpp0<0xB1>(v));
+    v = fmaxf(v, dpp0<0x4E>(v));
+    v = fmaxf(v, dpp0<0x141>(v));
+#endif
+    return v;
+}
+#else
+template <int S>
+inline void affine_shr(float* R, float* p)
+{
+    float A[9], a3[3], n[12];
+    for (int a = 0; a < 9; a++) A[a] = row_shr<S>(R[a], (a % 4 == 0) ? 1.f : 0.f);
+    for (int a = 0; a < 3; a++) a3[a] = row_shr<S>(p[a], 0.f);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) n[3 * i + j] = A[3 * i] * R[j] + A[3 * i + 1] * R[3 + j] + A[3 * i + 2] * R[6 + j];
+        const float t = A[3 * i] * p[0] + A[3 * i + 1] * p[1] + A[3 * i + 2] * p[2];
+        n[9 + i] = a3[i] + t;
+    }
+    for (int a = 0; a < 9; a++) R[a] = n[a];
+    for (int a = 0; a < 3; a++) p[a] = n[9 + a];
+}
+inline void half_gram6(const float* x, float* s)
+{
+    int k = 0;
+    for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++) s[k++] = half_sum(x[a] * x[b]);
+}
+inline float half_max(float v)
+{
+    exchange_put<1>(&v);
+    const int b = lane() & ~7;
+    float s = xbuf()[b];
+    for (int k = 1; k < 8; k++) s = fmaxf(s, xbuf()[b + k]);
+    exchange_done();
+    return s;
+}
+#endif
+}  // namespace wv
+namespace wr {
+template <int S>
+__device__ __forceinline__ void affine_shr(float* R, float* p) { wv::affine_shr<S>(R, p); }
+__device__ __forceinline__ void half_gram6(const float* x, float* s) { wv::half_gram6(x, s); }
+__device__ __forceinline__ float half_max(float v) { return wv::half_max(v); }
+}  // namespace wr
+#endif
