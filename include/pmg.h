@@ -598,6 +598,80 @@ int64_t pmg_sac_target_work_floats(const pmg_mlp* actor, int has_next_action, in
 int pmg_sac_target_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic1_target,
                           const pmg_mlp* critic2_target /* NULL: one critic */, const pmg_sac_target* td);
 
+/* pmg_sac_policy_grad_device (normative), float32 throughout: the actor's half of a SAC update in one call -- the gradient of
+ *   lscale * alpha * sum_b log pi(a_b | x_b) + gscale * sum_b min(Q1, Q2)(x_b, a_b),   a_b = tanh(m + exp(ls) n)  (reparameterised: n is held fixed)
+ * with respect to the Gaussian actor's parameters, through the online critics.  SAC's actor loss mean(alpha log pi - min Q) is lscale = 1 / B,
+ * gscale = -1 / B.  alpha: the struct's, or *d_alpha when d_alpha is given (as pmg_sac_target).  Stream-ordered on the handle's stream, syncs
+ * nothing, writes only its outputs and d_work, touches no state of the handle; no network's weights are written.  Per row b,
+ * Dx = actor.width[0], A = actor.width[L] / 2:
+ *   1. z, n, sd = expf(ls), a, l_j and logp: the head above on x[b], sample index (row_offset + b) * A + j -- the bits pmg_sac_sample_device returns
+ *      for the same (seed, counter, row_offset + b).  d_action receives a, d_logp receives logp.
+ *   2. q_c = critic c's chain and output activation on the row x[b] | a.  d_q1 / d_q2 receive them.
+ *   3. ga_c[j]: critic c's backward as in pmg_policy_grad_device step 3, with the constant head gscale and input gradients only.
+ *   4. ga = (critic2 == NULL || q1 <= q2) ? ga1 : ga2: a tie takes critic 1, a NaN on either side critic 2.  d_gaction receives ga.
+ *   5. e = lscale * alpha (one multiply);  t = fmaf(-a, a, 1.f);  d = ga * t;  sdn = sd * n;
+ *        g_mu[j] = fmaf(2.f * e, a, d)
+ *        g_ls[j] = (z[A + j] >= ls_lo && z[A + j] <= ls_hi) ? fmaf(e, fmaf(2.f * a, sdn, -1.f), d * sdn) : +0.0f
+ *      -- the clamp's derivative, inclusive at both ends as torch.clamp's is; a NaN z takes the +0.0 branch.  d_ghead receives g_mu | g_ls.
+ *   6. delta_{L-1} = g_mu | g_ls, and from there dW_l and db_l of the actor exactly as pmg_mlp_grad_device (chunk_rows == 0) or
+ *      pmg_mlp_grad_chunked_device (chunk_rows >= 2, even) forms them from d_gout = g.
+ * grads == NULL: steps 5 and 6 run only when d_ghead is given, and the actor's part of the workspace is not touched.  Without grads, d_gaction
+ * and d_ghead no critic backward runs; with d_action / d_logp alone no critic runs at all.
+ * A row's outputs do not depend on the batch it is in; dW and db depend on the row order and on chunk_rows and on nothing else; nothing depends
+ * on the grid; two calls on the same inputs give the same bits.  A <= 128 and Dx + A <= 256.
+ * Workspace: pmg_sac_policy_grad_work_floats = the actor's pmg_mlp_grad_work_floats (chunk_rows == 0) or pmg_mlp_grad_chunked_work_floats figure,
+ * laid out as those calls lay it out, + batch * A without d_action (a has to be kept for the critics somewhere) + batch * A with a second
+ * critic (ga1 while critic 2 runs); < 0 for an invalid actor, batch or chunk_rows.  Between the head and step 5, sd n and the predicate of a
+ * (row, unit) are kept where its delta_{L-1} will be (without grads: in d_ghead).
+ * PMG_E_INVALID, with nothing launched and nothing written: everything pmg_sac_target_device rejects in the networks, alpha, d_alpha, ls_lo,
+ * ls_hi and row_offset; everything pmg_policy_grad_device rejects in grads, strides, pointers, chunk_rows, d_work and work_floats; gscale or
+ * lscale not finite; grads and every output NULL; a wrong struct_size.  batch == 0 is a successful no-op that leaves grads untouched. */
+typedef struct pmg_sac_policy_grad {
+    int32_t struct_size, reserved;
+    float gscale;                        /* finite; -1 / B for -mean min(Q1, Q2) */
+    float lscale;                        /* finite; 1 / B for alpha * mean log pi; 0: no entropy term */
+    float alpha;                         /* >= 0, finite: the temperature (not read when d_alpha is given) */
+    float ls_lo, ls_hi;                  /* as pmg_sac_sample */
+    int32_t sample, reserved2;
+    uint64_t seed, counter;
+    int64_t row_offset;
+    int64_t batch;
+    const float* d_alpha;                /* NULL, or one float in device memory that replaces alpha */
+    const float* d_x; int64_t x_stride;            /* [B, Dx] */
+    const pmg_mlp_params* grads;         /* the ACTOR's dW / db, overwritten; NULL: the outputs below only */
+    float* d_action; int64_t action_stride;        /* [B, A]   or NULL: a */
+    float* d_logp;                                 /* [B]      or NULL: log pi(a | x) */
+    float* d_q1; float* d_q2;                      /* [B]      or NULL each (d_q2 is not written without a second critic) */
+    float* d_gaction; int64_t gaction_stride;      /* [B, A]   or NULL: ga of the critic with the smaller Q */
+    float* d_ghead; int64_t ghead_stride;          /* [B, 2 A] or NULL: g_mu | g_ls, the gradient at the actor's outputs */
+    float* d_work; int64_t work_floats;  /* scratch, at least pmg_sac_policy_grad_work_floats(actor, d_action != NULL, critic2 != NULL, batch, chunk_rows) */
+} pmg_sac_policy_grad;
+int64_t pmg_sac_policy_grad_work_floats(const pmg_mlp* actor, int has_action, int has_critic2, int64_t batch, int64_t chunk_rows);
+int pmg_sac_policy_grad_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic1, const pmg_mlp* critic2 /* NULL: one critic */,
+                               const pmg_sac_policy_grad* g, int64_t chunk_rows);
+
+/* pmg_sac_alpha_device (normative), float32: one Adam step on SAC's log-temperature from the log-probabilities of a batch.
+ * d_state: four caller-owned floats in device memory, log_alpha | m | v | alpha; pass d_state + 3 as d_alpha to pmg_sac_target_device and
+ * pmg_sac_policy_grad_device.  Stream-ordered on the handle's stream, syncs nothing, writes d_state only.
+ *   1. p_t = +0.0f;  p_t = p_t + logp[b] over the rows b = t (mod 256) in ascending order, t = 0 ... 255.
+ *   2. total = +0.0f;  total = total + p_t, t ascending: ONE chain.  Bit-defined; nothing depends on a grid.
+ *   3. g = -(total / (float)batch + target_entropy), the quotient correctly rounded: the gradient of -log_alpha * mean(logp + target_entropy).
+ *   4. pmg_mlp_adam_device's step on log_alpha with g (m and v beside it), bit for bit.
+ *   5. alpha = expf(log_alpha) into d_state[3].
+ * PMG_E_INVALID, with nothing launched: batch <= 0; target_entropy not finite; everything pmg_mlp_adam_device rejects in lr, the betas, eps and
+ * step; d_logp or d_state NULL or off 4 bytes; a wrong struct_size. */
+typedef struct pmg_sac_alpha {
+    int32_t struct_size, reserved;
+    float target_entropy;                /* finite; SAC: -A */
+    float lr, beta1, beta2, eps;         /* as pmg_adam */
+    int32_t reserved2;
+    int64_t step;                        /* t >= 1 */
+    int64_t batch;
+    const float* d_logp;                 /* [B] */
+    float* d_state;                      /* [4]: log_alpha, m, v, alpha */
+} pmg_sac_alpha;
+int pmg_sac_alpha_device(pmg_env* env, const pmg_sac_alpha* a);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

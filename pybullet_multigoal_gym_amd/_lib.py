@@ -108,6 +108,20 @@ class PmgPolicyGrad(C.Structure):
                 ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
 
 
+class PmgSacPolicyGrad(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gscale', C.c_float), ('lscale', C.c_float), ('alpha', C.c_float), ('ls_lo', C.c_float),
+                ('ls_hi', C.c_float), ('sample', C.c_int32), ('reserved2', C.c_int32), ('seed', C.c_uint64), ('counter', C.c_uint64), ('row_offset', C.c_int64),
+                ('batch', C.c_int64), ('d_alpha', C.c_void_p), ('d_x', C.c_void_p), ('x_stride', C.c_int64), ('grads', C.POINTER(PmgMlpParams)),
+                ('d_action', C.c_void_p), ('action_stride', C.c_int64), ('d_logp', C.c_void_p), ('d_q1', C.c_void_p), ('d_q2', C.c_void_p),
+                ('d_gaction', C.c_void_p), ('gaction_stride', C.c_int64), ('d_ghead', C.c_void_p), ('ghead_stride', C.c_int64), ('d_work', C.c_void_p),
+                ('work_floats', C.c_int64)]
+
+
+class PmgSacAlpha(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('target_entropy', C.c_float), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float),
+                ('eps', C.c_float), ('reserved2', C.c_int32), ('step', C.c_int64), ('batch', C.c_int64), ('d_logp', C.c_void_p), ('d_state', C.c_void_p)]
+
+
 class PmgAdam(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
                 ('step', C.c_int64)]
@@ -136,7 +150,8 @@ class PmgLibrary:
                'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
                'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device',
                'pmg_td3_target_work_floats', 'pmg_td3_target_device',
-               'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device']
+               'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device',
+               'pmg_sac_policy_grad_work_floats', 'pmg_sac_policy_grad_device', 'pmg_sac_alpha_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -162,6 +177,7 @@ class PmgLibrary:
         L.pmg_policy_grad_work_floats.restype = C.c_int64
         L.pmg_td3_target_work_floats.restype = C.c_int64
         L.pmg_sac_target_work_floats.restype = C.c_int64
+        L.pmg_sac_policy_grad_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -461,6 +477,37 @@ class PmgHandle:
         host sync."""
         self._check(self.L.lib.pmg_sac_target_device(self.h, C.byref(actor), C.byref(critic1_target),
                                                      C.byref(critic2_target) if critic2_target is not None else None, C.byref(td)))
+
+    # -- SAC: the actor's half in one call and the temperature step (include/pmg.h, DESIGN.md 3.16) --
+    @staticmethod
+    def sac_policy_grad_struct(batch, d_x, x_stride, d_work, work_floats, gscale, lscale, alpha=0.0, ls_lo=-20.0, ls_hi=2.0, sample=1, seed=0, counter=0,
+                               row_offset=0, d_alpha=None, grads=None, d_action=None, action_stride=0, d_logp=None, d_q1=None, d_q2=None, d_gaction=None,
+                               gaction_stride=0, d_ghead=None, ghead_stride=0):
+        """pmg_sac_policy_grad from device pointers (integers or None); grads: a params_struct() or None (it must outlive the call)."""
+        return PmgSacPolicyGrad(C.sizeof(PmgSacPolicyGrad), 0, gscale, lscale, alpha, ls_lo, ls_hi, int(bool(sample)), 0, seed & (2 ** 64 - 1),
+                                counter & (2 ** 64 - 1), row_offset, batch, d_alpha, d_x, x_stride, C.pointer(grads) if grads is not None else None,
+                                d_action, action_stride, d_logp, d_q1, d_q2, d_gaction, gaction_stride, d_ghead, ghead_stride, d_work, work_floats)
+
+    def sac_policy_grad_work_floats(self, actor, has_action, has_critic2, batch, chunk_rows=0):
+        """floats of workspace pmg_sac_policy_grad_device needs: the actor's gradient figure, + batch * A without d_action, + batch * A with a second
+        critic (< 0: invalid)"""
+        return int(self.L.lib.pmg_sac_policy_grad_work_floats(C.byref(actor), C.c_int(bool(has_action)), C.c_int(bool(has_critic2)), C.c_int64(batch),
+                                                              C.c_int64(chunk_rows)))
+
+    def sac_policy_grad_device(self, actor, critic1, critic2, grad, chunk_rows=0):
+        """the Gaussian actor's gradient of lscale alpha sum log pi + gscale sum min(Q1, Q2) of a sac_policy_grad_struct(); critic2 may be None;
+        stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_sac_policy_grad_device(self.h, C.byref(actor), C.byref(critic1), C.byref(critic2) if critic2 is not None else None,
+                                                          C.byref(grad), C.c_int64(chunk_rows)))
+
+    @staticmethod
+    def sac_alpha_struct(batch, d_logp, d_state, target_entropy, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
+        """pmg_sac_alpha from device pointers; d_state: four floats, log_alpha | m | v | alpha."""
+        return PmgSacAlpha(C.sizeof(PmgSacAlpha), 0, target_entropy, lr, beta1, beta2, eps, 0, step, batch, d_logp, d_state)
+
+    def sac_alpha_device(self, a):
+        """one Adam step on the log-temperature of a sac_alpha_struct(), then alpha = exp(log_alpha); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_sac_alpha_device(self.h, C.byref(a)))
 
     # -- back-propagation, Adam, Polyak (include/pmg.h, DESIGN.md 3.11) --
     @staticmethod

@@ -1553,6 +1553,127 @@ int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* crit
     return PMG_OK;
 }
 
+/* ---- SAC's actor half in one call and the temperature step ---- */
+/* the actor's figure, then a [B, A] without d_action, then critic 1's ga [B, A] with a second critic */
+int64_t pmg_sac_policy_grad_work_floats(const pmg_mlp* actor, int has_action, int has_critic2, int64_t batch, int64_t chunk_rows)
+{
+    const int64_t base = chunk_rows == 0 ? pmg_mlp_grad_work_floats(actor, batch) : pmg_mlp_grad_chunked_work_floats(actor, batch, chunk_rows);
+    if (base < 0) return -1;
+    const int A2 = actor->width[actor->num_layers];
+    if (A2 < 2 || (A2 & 1) != 0) return -1;
+    return base + (has_action ? 0 : batch * (A2 / 2)) + (has_critic2 ? batch * (A2 / 2) : 0);
+}
+
+int pmg_sac_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic1, const pmg_mlp* critic2, const pmg_sac_policy_grad* g, int64_t chunk_rows)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_sac_policy_grad_device";
+    PmgMlp P, Q1, Q2;
+    if (int rc = mlp_of(e, actor, "pmg_sac_policy_grad_device (actor)", P)) return rc;
+    if (int rc = gaussian_of(e, P, "pmg_sac_policy_grad_device (actor)")) return rc;
+    if (int rc = mlp_of(e, critic1, "pmg_sac_policy_grad_device (critic 1)", Q1)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L] / 2;
+    if (int rc = critic_of(e, Q1, Dx + A, "pmg_sac_policy_grad_device (critic 1)")) return rc;
+    if (critic2) {
+        if (int rc = mlp_of(e, critic2, "pmg_sac_policy_grad_device (critic 2)", Q2)) return rc;
+        if (int rc = critic_of(e, Q2, Dx + A, "pmg_sac_policy_grad_device (critic 2)")) return rc;
+    } else
+        Q2 = Q1;
+    if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
+    if (g->struct_size != (int32_t)sizeof(pmg_sac_policy_grad)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_sac_policy_grad));
+    if (g->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)g->batch);
+    if (!g->d_x) return fail(e, PMG_E_INVALID, "%s: d_x is null", who);
+    if (!std::isfinite(g->gscale) || !std::isfinite(g->lscale)) return fail(e, PMG_E_INVALID, "%s: gscale %g or lscale %g is not finite", who, (double)g->gscale, (double)g->lscale);
+    if (!(g->alpha >= 0.f) || std::isinf(g->alpha)) return fail(e, PMG_E_INVALID, "%s: alpha %g must be finite and >= 0", who, (double)g->alpha);
+    if (int rc = sac_clamp_of(e, g->ls_lo, g->ls_hi, who)) return rc;
+    if (g->row_offset < 0) return fail(e, PMG_E_INVALID, "%s: row_offset %lld is negative", who, (long long)g->row_offset);
+    float* const d_q2 = critic2 ? g->d_q2 : nullptr;
+    if (!g->grads && !g->d_action && !g->d_logp && !g->d_q1 && !d_q2 && !g->d_gaction && !g->d_ghead)
+        return fail(e, PMG_E_INVALID, "%s: grads, d_action, d_logp, d_q1, d_q2, d_gaction and d_ghead are all null: nothing to do", who);
+    if (g->grads) if (int rc = params_of(e, P, g->grads, false, who, "grads")) return rc;
+    if ((((size_t)g->d_x | (size_t)g->d_alpha | (size_t)g->d_action | (size_t)g->d_logp | (size_t)g->d_q1 | (size_t)g->d_q2 | (size_t)g->d_gaction | (size_t)g->d_ghead |
+          (size_t)g->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (g->x_stride < Dx || (g->d_action && g->action_stride < A) || (g->d_gaction && g->gaction_stride < A) || (g->d_ghead && g->ghead_stride < 2 * A))
+        return fail(e, PMG_E_INVALID, "%s: a stride is smaller than its width", who);
+    if (chunk_rows < 0 || chunk_rows == 1 || (chunk_rows & 1)) return fail(e, PMG_E_INVALID, "%s: chunk_rows %lld must be 0 (one chain) or even and >= 2", who, (long long)chunk_rows);
+    const int64_t C = chunk_rows ? g->batch / chunk_rows + (g->batch % chunk_rows != 0) : 1;
+    if (C > PMG_GRAD_MAX_CHUNKS)
+        return fail(e, PMG_E_INVALID, "%s: batch %lld in chunks of %lld rows is %lld chunks, more than %d", who, (long long)g->batch, (long long)chunk_rows, (long long)C, PMG_GRAD_MAX_CHUNKS);
+    const bool chunked = g->grads && C > 1;
+    const int64_t base = pmg_mlp_grad_work_floats(actor, g->batch);
+    const int64_t mine = chunked ? pmg_mlp_grad_chunked_work_floats(actor, g->batch, chunk_rows) : base;   /* the actor's part of the workspace */
+    if (mine < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)g->batch);
+    const int64_t need = mine + (g->d_action ? 0 : g->batch * A) + (critic2 ? g->batch * A : 0);
+    if (!g->d_work || g->work_floats < need) return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld < %lld", who, (long long)g->work_floats, (long long)need);
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = Q1.B = Q2.B = g->batch;
+    PmgGrad G;
+    memset(&G, 0, sizeof(G));
+    G.x = g->d_x; G.xs = g->x_stride; G.x_dim = Dx;
+    G.grads = g->grads ? 1 : 0;
+    for (int l = 0; l < P.L && g->grads; l++) { G.dw[l] = g->grads->d_weight[l]; G.db[l] = P.b[l] ? g->grads->d_bias[l] : nullptr; }
+    pmg_grad_work_layout(P, P.B, g->d_work, &G);
+    PmgSacPolicy X;
+    memset(&X, 0, sizeof(X));
+    X.H.ls_lo = g->ls_lo; X.H.ls_hi = g->ls_hi; X.H.sample = g->sample != 0; X.H.seed = g->seed; X.H.counter = g->counter;
+    X.H.row_offset = (unsigned long long)g->row_offset;
+    X.H.logp = g->d_logp;
+    float* extra = g->d_work + mine;
+    if (g->d_action) { X.H.action = g->d_action; X.H.as = g->action_stride; }
+    else { X.H.action = extra; X.H.as = A; extra += g->batch * A; }
+    X.gscale = g->gscale; X.lscale = g->lscale; X.alpha = g->alpha; X.d_alpha = g->d_alpha;
+    X.twin = critic2 != nullptr;
+    X.q1 = g->d_q1; X.q2 = d_q2;
+    X.ga = g->d_gaction; X.gas = g->gaction_stride;
+    X.ghead = g->d_ghead; X.ghs = g->ghead_stride;
+    if (g->grads) { X.stash = G.wd[P.L - 1]; X.ss = 2 * A; }
+    else if (g->d_ghead) { X.stash = g->d_ghead; X.ss = g->ghead_stride; }
+    X.ga1 = critic2 ? extra : nullptr;
+    if (!chunked) {
+        HIP_TRY(e, pmg_launch_sac_policy_grad(P, Q1, Q2, G, X, nullptr, nullptr, e->stream));
+        return PMG_OK;
+    }
+    PmgSegs T;
+    segs_of(P, g->grads, g->grads->d_weight, g->grads->d_bias, nullptr, nullptr, T);
+    PmgGradChunks K;
+    memset(&K, 0, sizeof(K));
+    K.R = chunk_rows; K.C = C; K.P = grad_chunk_params(actor); K.tiles = pmg_grad_w_tiles(P); K.part = g->d_work + base;
+    for (int l = 0, n = 0; l < P.L; l++) {                          /* tensor n of T starts at T.end[n - 1] */
+        K.pw[l] = K.part + (n ? T.end[n - 1] : 0);
+        n++;
+        if (P.b[l]) { K.pb[l] = K.part + T.end[n - 1]; n++; }
+    }
+    HIP_TRY(e, pmg_launch_sac_policy_grad(P, Q1, Q2, G, X, &K, &T, e->stream));
+    return PMG_OK;
+}
+
+int pmg_sac_alpha_device(pmg_env* e, const pmg_sac_alpha* a)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_sac_alpha_device";
+    if (!a) return fail(e, PMG_E_INVALID, "%s: a is null", who);
+    if (a->struct_size != (int32_t)sizeof(pmg_sac_alpha)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, a->struct_size, sizeof(pmg_sac_alpha));
+    if (a->batch <= 0) return fail(e, PMG_E_INVALID, "%s: batch %lld must be >= 1", who, (long long)a->batch);
+    if (!std::isfinite(a->target_entropy)) return fail(e, PMG_E_INVALID, "%s: target_entropy %g is not finite", who, (double)a->target_entropy);
+    if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !(a->eps >= 0.f)) return fail(e, PMG_E_INVALID, "%s: lr %g must be finite, eps %g finite and >= 0", who, (double)a->lr, (double)a->eps);
+    if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return fail(e, PMG_E_INVALID, "%s: betas %g / %g must lie in [0, 1)", who, (double)a->beta1, (double)a->beta2);
+    if (a->step < 1) return fail(e, PMG_E_INVALID, "%s: step %lld must be >= 1", who, (long long)a->step);
+    if (!a->d_logp || !a->d_state) return fail(e, PMG_E_INVALID, "%s: d_logp or d_state is null", who);
+    if ((((size_t)a->d_logp | (size_t)a->d_state) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    /* pmg_mlp_adam_device's derived constants */
+    const double c1 = 1.0 - pow((double)a->beta1, (double)a->step), c2 = 1.0 - pow((double)a->beta2, (double)a->step);
+    PmgSacAlpha X;
+    X.logp = a->d_logp; X.B = a->batch; X.target_entropy = a->target_entropy; X.state = a->d_state;
+    X.A.beta1 = a->beta1; X.A.beta2 = a->beta2;
+    X.A.omb1 = (float)(1.0 - (double)a->beta1); X.A.omb2 = (float)(1.0 - (double)a->beta2);
+    X.A.step_size = (float)((double)a->lr / c1); X.A.rsc2 = (float)(1.0 / sqrt(c2)); X.A.eps = a->eps;
+    HIP_TRY(e, pmg_launch_sac_alpha(X, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

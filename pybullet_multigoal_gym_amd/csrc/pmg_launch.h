@@ -171,6 +171,33 @@ struct PmgPolicy {
 };
 hipError_t pmg_launch_policy_grad(const PmgMlp& actor, const PmgMlp& critic, const PmgGrad& G, const PmgPolicy& X, const PmgGradChunks* Q,
                                   const PmgSegs* T, hipStream_t s);
+/* SAC's actor half in one call (pmg_sac_policy_grad_device), validated by the caller.  actor.B = critic.B rows of G.x
+ * [B, actor.width[0]]; G carries the ACTOR's arguments as for pmg_launch_policy_grad (grads, dw / db, wh / wd; everything else null).  H: the
+ * head's arguments, H.action / H.as = where a [B, A] is written and read back in front of every critic (the caller's d_action at its stride,
+ * else the workspace at A; never null), H.logp may be null, H.noise and H.preact are null.  stash / ss: two floats per (row, unit) between the
+ * head and the hand-back -- the actor's delta_{L-1} slot (ss = 2 A) with grads, else ghead at ghs; null when neither is given.  ga1 [B, A]
+ * contiguous: critic 1's ga while critic 2 owns the tile (twin and a backward only).  d_alpha: a device scalar that replaces alpha when not
+ * null.  critic2 is read only when twin != 0.  Q / T: the chunked reduction as for pmg_launch_policy_grad. */
+struct PmgSacPolicy {
+    PmgSac H;
+    float gscale, lscale, alpha; const float* d_alpha;
+    int twin;
+    float* q1; float* q2;
+    float* ga; long long gas;
+    float* ghead; long long ghs;
+    float* stash; long long ss;
+    float* ga1;
+};
+hipError_t pmg_launch_sac_policy_grad(const PmgMlp& actor, const PmgMlp& critic1, const PmgMlp& critic2, const PmgGrad& G, const PmgSacPolicy& X,
+                                      const PmgGradChunks* Q, const PmgSegs* T, hipStream_t s);
+/* SAC's temperature step (pmg_sac_alpha_device), validated by the caller: state = log_alpha | m | v | alpha */
+struct PmgSacAlpha {
+    const float* logp; long long B;
+    float target_entropy;
+    PmgAdam A;
+    float* state;
+};
+hipError_t pmg_launch_sac_alpha(const PmgSacAlpha& X, hipStream_t s);
 hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
 #endif

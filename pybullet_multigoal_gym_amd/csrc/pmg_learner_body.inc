@@ -1551,3 +1551,206 @@ hipError_t pmg_launch_policy_grad(const PmgMlp& P, const PmgMlp& Q, const PmgGra
     }
     return hipGetLastError();
 }
+
+/* SAC's actor half in one call (pmg_sac_policy_grad_device, DESIGN.md 3.16), pmg_k_policy_grad_rows' sibling for the Gaussian actor: the actor's
+ * forward, pmg_k_sac_target's head, either critic's forward on x | a and its input-only backward, the selection of ga by q1 <= q2, the head
+ * gradient and the actor's transposed layers on ONE tile, then the weights kernel of 3.11 (or the partials / merge pair of 3.12), unchanged,
+ * on the actor's workspace.
+ * Forward: nothing is handed to the critics through the tile (the hazard of 3.15: the actor leaves 2 A columns).  Thread (row, unit j) of
+ * pmg_k_sac's map writes a to X.H.action (the caller's d_action, or the workspace), l_j into its own column j and, when the head gradient
+ * will run, sd n and the in-range predicate (1.0 / 0.0) into X.stash -- two floats per (row, unit): the actor's delta_{L-1} slot, or d_ghead
+ * without grads.  The SAME thread reads them back in the hand-back and overwrites them with g_mu | g_ls, and the same thread writes critic
+ * 1's ga to X.ga1 and reads it back behind critic 2: a thread reads only its own earlier stores, so no ordering between threads is involved.
+ * x | a is rebuilt in front of each critic by sac_rebuild's map (sac_rebuild_at: the kept action may sit at a stride).
+ * Hand-back: ga sits in columns [Dx, Dx + A), g_mu | g_ls go to columns [0, 2 A), which overlap them when Dx < 2 A.  The passes (256
+ * (row, unit) pairs of the head's map each) read their ga one pass AHEAD of their writes: behind the barrier of pass k the ga of the passes up to
+ * k + 1 are in registers (two per thread), and passes k and k + 2 share no row (A <= 128 < 256), so no write reaches a ga still to be read.
+ * Columns [0, 2 A) are written for all 32 rows, +0.0 past the batch; 2 A is even, so the actor's first transposed chain reads no padding
+ * column and nothing stale.
+ * Which critic supplies ga is a per-row flag in LDS beside the tile, written by the row's thread (t < 32) in front of the barrier that
+ * precedes critic 2's backward; the same word holds q1 for that thread while critic 2 runs. */
+__device__ __forceinline__ void sac_rebuild_at(float* tile, const MlpRawRows& S, const float* keep, long long ks, long long row0, long long B, int Dx, int A,
+                                               int t)
+{
+    mlp_gather(tile, S, row0, B, Dx, Dx, t);
+    for (int i = t; i < MLP_ROWS * A; i += 256) {                    /* the head's map: a thread reads what it stored itself */
+        const int r = i / A, j = i - r * A;
+        tile[r * MLP_LD + Dx + j] = row0 + r < B ? keep[(row0 + r) * ks + j] : 0.f;
+    }
+    if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+}
+/* a critic's output of the row's thread (t < 32; +0.0 elsewhere) and, when its backward will run, the constant head into column 0 of all 32
+ * rows (rows past the batch: +0.0); column 1, the padding of the single output, is +0.0 from the last layer's whole strip */
+__device__ __forceinline__ float sac_pg_qhead(float* tile, const PmgMlp& Q, float gscale, bool back, bool own, int t)
+{
+    float q = 0.f;
+    if (t < MLP_ROWS) {
+        float d = 0.f;
+        if (own) {
+            const float z = tile[t * MLP_LD];
+            q = Q.out_act ? tanhf(z) : z;
+            d = Q.out_act ? gscale * fmaf(-q, q, 1.f) : gscale;
+        }
+        if (back) tile[t * MLP_LD] = d;
+    }
+    return q;
+}
+/* both critics as ONE kernel argument: the pass over the critics picks its network by a run-time index into the argument itself, which stays
+ * in the kernel-argument segment (two arguments picked by a select are copied to scratch: 384 bytes per lane) */
+struct PmgMlpPair { PmgMlp q[2]; };
+/* P: the actor, QQ: the critics (q[1] is read only when X.twin), G: the actor's gradient arguments as for pmg_k_policy_grad_rows */
+__global__ void __launch_bounds__(256, 2) pmg_k_sac_policy_grad_rows(PmgMlp P, PmgMlpPair QQ, PmgGrad G, PmgSacPolicy X)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    __shared__ float sel[MLP_ROWS];                              /* row r of the tile: q1 while critic 2 runs (its own thread's), then 1.0 where critic 1 supplies ga */
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L] >> 1;
+    const MlpRawRows S = {G.x, G.xs};
+    float* keep = X.H.action;
+    const long long ks = X.H.as;
+    const bool headgrad = X.stash != nullptr, back = headgrad || X.ga, critic = back || X.q1 || X.q2;
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        unsigned int am1 = 0, am2 = 0, am3 = 0, cm1 = 0, cm2 = 0, cm3 = 0;
+        mlp_layers_saved(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+        for (int i = t; i < MLP_ROWS * A; i += 256) {            /* the head, pmg_k_sac_target's pass */
+            const int r = i / A, j = i - r * A;
+            const long long row = row0 + r;
+            if (row >= P.B) break;
+            const float ls = tile[r * MLP_LD + A + j];
+            const SacHead h = sac_head(X.H, tile[r * MLP_LD + j], ls, (X.H.row_offset + (unsigned long long)row) * (unsigned long long)A + (unsigned long long)j);
+            keep[row * ks + j] = h.a;
+            tile[r * MLP_LD + j] = h.l;
+            if (headgrad) {
+                const float sd = expf(fminf(fmaxf(ls, X.H.ls_lo), X.H.ls_hi));   /* sac_head's sd */
+                X.stash[row * X.ss + j] = sd * h.n;
+                X.stash[row * X.ss + A + j] = (ls >= X.H.ls_lo && ls <= X.H.ls_hi) ? 1.f : 0.f;
+            }
+        }
+        __syncthreads();                                         /* every l_j of the tile is written */
+        const bool own = t < MLP_ROWS && row0 + t < P.B;         /* this thread forms the outputs of row row0 + t */
+        if (own && X.H.logp) X.H.logp[row0 + t] = sac_logp(tile, t, A);
+        if (critic) {
+            /* ONE call site for both critics: Q is a reference into the kernel's own arguments, picked per pass */
+#pragma unroll 1
+            for (int c = 0; c <= X.twin; c++) {
+                const PmgMlp& Q = QQ.q[c];
+                if (c && back)
+                    for (int i = t; i < MLP_ROWS * A; i += 256) {    /* critic 1's ga out of critic 2's way, by the head's map */
+                        const int r = i / A, j = i - r * A;
+                        if (row0 + r >= P.B) break;
+                        X.ga1[(row0 + r) * A + j] = tile[r * MLP_LD + Dx + j];
+                    }
+                __syncthreads();                                 /* the sums (c == 1: q1 and ga) are read: the tile is free */
+                sac_rebuild_at(tile, S, keep, ks, row0, P.B, Dx, A, t);
+                __syncthreads();
+                mlp_layers_masked(tile, Q, lane, wave, col, cm1, cm2, cm3);
+                const float q = sac_pg_qhead(tile, Q, X.gscale, back, own, t);
+                float* __restrict__ qo = c ? X.q2 : X.q1;
+                if (own && qo) qo[row0 + t] = q;
+                /* q1 waits in LDS for its own thread; then the word becomes the flag: a tie takes critic 1, a NaN on either side critic 2 */
+                if (t < MLP_ROWS && X.twin) sel[t] = c ? (sel[t] <= q ? 1.f : 0.f) : q;
+                if (back) {
+                    __syncthreads();
+                    mlp_backward_action(tile, Q, Dx, nullptr, 0, row0, lane, wave, col, cm1, cm2, cm3);
+                }
+            }
+        }
+        if (back) {
+            /* the hand-back: ga in columns [Dx, Dx + A) -> g_mu | g_ls in columns [0, 2 A), in passes of 256 (row, unit) pairs of the head's map.  A
+             * pass reads its ga one pass AHEAD of its writes: behind the barrier of pass k the ga of the passes up to k + 1 are in registers, so
+             * the writes of pass k cannot reach a ga still to be read -- passes k and k + 2 share no row (A <= 128 < 256) */
+            const float e = X.lscale * (X.d_alpha ? *X.d_alpha : X.alpha);
+            const int n = MLP_ROWS * A;
+            float cur = t < n ? tile[(t / A) * MLP_LD + Dx + t % A] : 0.f;
+#pragma unroll 1
+            for (int i = t; i - t < n; i += 256) {
+                const int in = i + 256, rn = in / A;
+                const float nxt = in < n ? tile[rn * MLP_LD + Dx + (in - rn * A)] : 0.f;
+                if (headgrad) __syncthreads();                   /* the ga of this pass and of the next are read */
+                if (i < n) {
+                    const int r = i / A, j = i - r * A;
+                    const long long row = row0 + r;
+                    float gm = 0.f, gl = 0.f;
+                    if (row < P.B) {
+                        const float ga = X.twin && sel[r] != 0.f ? X.ga1[row * A + j] : cur;
+                        if (X.ga) X.ga[row * X.gas + j] = ga;
+                        if (headgrad) {
+                            const float a = keep[row * ks + j], sdn = X.stash[row * X.ss + j];
+                            const bool inr = X.stash[row * X.ss + A + j] != 0.f;
+                            const float d = ga * fmaf(-a, a, 1.f);
+                            gm = fmaf(2.f * e, a, d);
+                            gl = inr ? fmaf(e, fmaf(2.f * a, sdn, -1.f), d * sdn) : 0.f;
+                            if (X.ghead) { X.ghead[row * X.ghs + j] = gm; X.ghead[row * X.ghs + A + j] = gl; }
+                            /* with grads the stash IS the actor's delta_{L-1} slot: the same pointer, so the stores stay behind the loads above */
+                            if (G.grads) { X.stash[row * X.ss + j] = gm; X.stash[row * X.ss + A + j] = gl; }
+                        }
+                    }
+                    if (headgrad) { tile[r * MLP_LD + j] = gm; tile[r * MLP_LD + A + j] = gl; }
+                }
+                cur = nxt;
+            }
+            if (G.grads) {
+                __syncthreads();
+                mlp_backward(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+            }
+        }
+        __syncthreads();                                         /* the next tile's rows overwrite this one's */
+    }
+}
+hipError_t pmg_launch_sac_policy_grad(const PmgMlp& P, const PmgMlp& Q1, const PmgMlp& Q2, const PmgGrad& G, const PmgSacPolicy& head, const PmgGradChunks* C,
+                                      const PmgSegs* T, hipStream_t s)
+{
+    if (P.B <= 0) return hipSuccess;
+    PmgSacPolicy X = head;
+    X.H.key = her_mix(X.H.seed ^ her_mix(X.H.counter + HER_GOLD));
+    PmgMlpPair QQ;
+    QQ.q[0] = Q1; QQ.q[1] = Q2;
+    hipLaunchKernelGGL(pmg_k_sac_policy_grad_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, QQ, G, X);
+    if (G.grads) {
+        const MlpRawRows S = {G.x, G.xs};
+        if (!C) hipLaunchKernelGGL((pmg_k_mlp_grad_weights<MlpRawRows>), dim3(pmg_grad_w_tiles(P)), dim3(64), 0, s, S, P, G);
+        else {
+            hipLaunchKernelGGL((pmg_k_mlp_grad_partials<MlpRawRows>), dim3((unsigned)(C->C * C->tiles)), dim3(64), 0, s, S, P, G, *C);
+            hipLaunchKernelGGL(pmg_k_mlp_grad_merge, dim3(seg_grid(*T)), dim3(256), 0, s, *T, (const float*)C->part, C->C, C->P);
+        }
+    }
+    return hipGetLastError();
+}
+
+/* SAC's temperature step (pmg_sac_alpha_device, DESIGN.md 3.16): one workgroup.  Thread t sums logp over the rows b = t (mod 256) in ascending
+ * order from +0.0; thread 0 adds the 256 partial sums in ascending order from +0.0, forms g = -(total / B + target_entropy), takes pmg_k_adam's
+ * step on log_alpha (adam_element restates that kernel's three expressions; the tests hold the two bit for bit) and stores alpha =
+ * expf(log_alpha).  The quotient is formed in double and rounded to float: with 53 >= 2 * 24 + 2 bits that IS the correctly rounded float32
+ * quotient, whatever the build does with float32 division. */
+__device__ __forceinline__ void adam_element(const PmgAdam& A, float g, float& p, float& m, float& v)
+{
+    m = fmaf(A.beta1, m, A.omb1 * g);
+    v = fmaf(A.beta2, v, A.omb2 * (g * g));
+    p = p - A.step_size * (m / (sqrtf(v) * A.rsc2 + A.eps));
+}
+__global__ void __launch_bounds__(256) pmg_k_sac_alpha(PmgSacAlpha X)
+{
+    __shared__ float part[256];
+    const int t = (int)threadIdx.x;
+    float p = 0.f;
+    for (long long b = t; b < X.B; b += 256) p = p + X.logp[b];
+    part[t] = p;
+    __syncthreads();
+    if (t == 0) {
+        float total = 0.f;
+        for (int i = 0; i < 256; i++) total = total + part[i];
+        const float g = -((float)((double)total / (double)(float)X.B) + X.target_entropy);
+        float la = X.state[0], m = X.state[1], v = X.state[2];
+        adam_element(X.A, g, la, m, v);
+        X.state[0] = la; X.state[1] = m; X.state[2] = v; X.state[3] = expf(la);
+    }
+}
+hipError_t pmg_launch_sac_alpha(const PmgSacAlpha& X, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_sac_alpha, dim3(1), dim3(256), 0, s, X);
+    return hipGetLastError();
+}
