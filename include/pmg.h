@@ -718,6 +718,67 @@ int pmg_comm_overlap(pmg_env* env, int32_t enabled);
 int pmg_allgather_packed_async(pmg_env* env, float* d_gathered);
 int pmg_allgather_wait(pmg_env* env, int32_t host);
 
+/* The data-parallel learner (normative): the rank-ordered merge of gradients and of the normalisers' totals, so that an
+ * update does not depend on how many GPUs its batch was spread over.  Every entry below is stream-ordered on the handle's stream, syncs
+ * nothing, writes only its outputs and its workspace and touches no env state.  The collectives (pmg_allgather_device,
+ * pmg_mlp_grad_allreduce_device, pmg_mlp_adam_allreduce_device, pmg_norm_update_ranks_device, pmg_norm_update_env_ranks_device) are one
+ * ncclAllGather of floats each (doubles travel as pairs of floats) and every rank must call them in the same order; they return PMG_E_STATE
+ * before pmg_comm_init, and PMG_E_STATE while pmg_comm_overlap is enabled: the overlapped all-gather runs on the handle's communication
+ * stream, and two streams must not issue collectives on one communicator -- switch the overlap off around a learner update.
+ *
+ * Gradients.  R ranks hold B_local rows each, B_local even and equal on all ranks; the global batch is the ranks' rows concatenated in rank
+ * order.  Each rank runs any gradient call as it is -- pmg_mlp_grad_device, pmg_policy_grad_device or pmg_sac_policy_grad_device, the single
+ * chain (chunk_rows = 0 / none) -- with the caller's gscale = ... / B_global: G_r.  After the merge
+ *   dW[i] = (...((G_0[i] + G_1[i]) + G_2[i]) ... + G_{R-1}[i]):  float32 additions in ascending rank order, one rounding each, starting from
+ * G_0[i] ITSELF, not from +0.0.  That is, by the definition of pmg_mlp_grad_chunked_device, bit for bit (zeros by value) what
+ * pmg_mlp_grad_chunked_device(chunk_rows = B_local) returns on the concatenated batch on one GPU.  A rank that chunks locally with
+ * chunk_rows = r, r dividing B_local, gets a function of the rows, their order, r and R alone; it is not claimed equal to any single-GPU
+ * call.  Every rank ends with the same bits.
+ *
+ * P = pmg_mlp_param_floats(shape) = the sum over the layers of width[l] * width[l + 1] + (d_bias[l] ? width[l + 1] : 0); a FLAT gradient is
+ * the network's tensors in that order -- weight 0, bias 0, weight 1, ... -- as P contiguous floats.  `shape` supplies the widths and which
+ * layers have a bias; its pointers are not dereferenced.  A SLOT is one rank's flat gradient; slot r lies at d_slots + r * slot_stride.
+ *   pmg_mlp_params_pack_device:  the tensors of src -> d_flat [P].
+ *   pmg_mlp_params_merge_device: the sum above over nslots >= 1 slots -> the tensors of out (one slot: a bit copy).
+ *   pmg_mlp_adam_merge_device:   the same sum handed to pmg_mlp_adam_device's step in one sweep: m and v bit for bit those of
+ *     pmg_mlp_params_merge_device followed by pmg_mlp_adam_device, p held to the same float64 model.  The summed gradient goes to
+ *     grad_out when given and is never stored otherwise.
+ *   pmg_mlp_grad_allreduce_device: pack, all-gather, merge back into grads, in place.
+ *   pmg_mlp_adam_allreduce_device: pack, all-gather, fused merge + Adam; grads keeps THIS rank's gradient.
+ *   Both take a workspace of pmg_mlp_allreduce_work_floats(env, shape) = (nranks + 1) * P floats (nranks = 1 before pmg_comm_init): this
+ *   rank's flat gradient in front, the gathered slots behind it.
+ *   pmg_allgather_device: count floats of every rank into d_gathered [nranks * count], rank order; count == 0 is a successful no-op.  A
+ *   data-parallel SAC learner gathers its logp rows with it and runs pmg_sac_alpha_device on the global [B] on every rank.
+ * PMG_E_INVALID, with nothing launched: a bad network shape; a NULL or misaligned tensor where the shape has one (a bias pointer where the
+ * shape has no bias is ignored); d_flat, d_slots, d_work, d_src or d_gathered NULL or off 4 bytes; nslots < 1; slot_stride < P; work_floats
+ * too small; count < 0; everything pmg_mlp_adam_device rejects in pmg_adam; a wrong struct_size.
+ *
+ * Normaliser.  A collective update with batch_local rows on every rank (equal on all ranks) cuts the rows at the chunk of the GLOBAL batch,
+ *   chunk = 64 * ceil(R * batch_local / (64 * 1022)),
+ * and batch_local must be a multiple of it unless R == 1 (PMG_E_INVALID otherwise, nothing launched).  Row 0 of rank r is global row
+ * r * batch_local; for the _env_ form num_envs is batch_local and env_index_offset must equal rank * num_envs (PMG_E_INVALID otherwise).
+ * Each rank forms its partial rows as pmg_norm_update_device does; gathered in rank order, [R][batch_local / chunk][2 D + 1] doubles, they are
+ * exactly the partial rows of the unsharded update in index order, and the same merge adds them onto the totals and re-derives mean / std /
+ * inv_std.  Totals and derived values are therefore bit-equal to ONE pmg_norm_update_device on the concatenated rows, and equal on every
+ * rank.  The gathered rows live in a buffer of the handle, allocated at the first collective update (a later larger one re-sizes it, which
+ * waits for the stream once) and freed by pmg_destroy.  PMG_E_INVALID: what pmg_norm_update_device rejects; d_rows off 4 bytes;
+ * batch_local < 0; batch_local == 0 is a successful no-op on every rank.  PMG_E_STATE (_env_ form): before the first reset. */
+int pmg_comm_info(pmg_env* env, int32_t* rank, int32_t* nranks);   /* of pmg_comm_init (either may be NULL); PMG_E_STATE before it */
+int pmg_allgather_device(pmg_env* env, const float* d_src, int64_t count, float* d_gathered);
+int64_t pmg_mlp_param_floats(const pmg_mlp* shape);   /* < 0: invalid network */
+int pmg_mlp_params_pack_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params* src, float* d_flat);
+int pmg_mlp_params_merge_device(pmg_env* env, const pmg_mlp* shape, const float* d_slots, int64_t slot_stride, int64_t nslots,
+                                const pmg_mlp_params* out);
+int pmg_mlp_adam_merge_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params* param, const float* d_slots, int64_t slot_stride,
+                              int64_t nslots, const pmg_mlp_params* grad_out /* or NULL */, const pmg_mlp_params* m, const pmg_mlp_params* v,
+                              const pmg_adam* a);
+int64_t pmg_mlp_allreduce_work_floats(const pmg_env* env, const pmg_mlp* shape);   /* < 0: invalid network */
+int pmg_mlp_grad_allreduce_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params* grads, float* d_work, int64_t work_floats);
+int pmg_mlp_adam_allreduce_device(pmg_env* env, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grads,
+                                  const pmg_mlp_params* m, const pmg_mlp_params* v, const pmg_adam* a, float* d_work, int64_t work_floats);
+int pmg_norm_update_ranks_device(pmg_env* env, int which, const float* d_rows, int64_t row_stride, int64_t batch_local, const uint8_t* d_mask);
+int pmg_norm_update_env_ranks_device(pmg_env* env, const uint8_t* d_mask);
+
 /* Device-buffer helpers for callers that have no HIP runtime of their own (e.g. a numpy-only
  * host): allocate / free / copy on the handle's device and stream.  Callers that already own
  * device memory (a torch tensor's data_ptr()) pass those pointers directly instead. */

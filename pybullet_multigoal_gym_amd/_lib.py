@@ -151,7 +151,10 @@ class PmgLibrary:
                'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device',
                'pmg_td3_target_work_floats', 'pmg_td3_target_device',
                'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device',
-               'pmg_sac_policy_grad_work_floats', 'pmg_sac_policy_grad_device', 'pmg_sac_alpha_device']
+               'pmg_sac_policy_grad_work_floats', 'pmg_sac_policy_grad_device', 'pmg_sac_alpha_device',
+               'pmg_comm_info', 'pmg_allgather_device', 'pmg_mlp_param_floats', 'pmg_mlp_params_pack_device', 'pmg_mlp_params_merge_device',
+               'pmg_mlp_adam_merge_device', 'pmg_mlp_allreduce_work_floats', 'pmg_mlp_grad_allreduce_device', 'pmg_mlp_adam_allreduce_device',
+               'pmg_norm_update_ranks_device', 'pmg_norm_update_env_ranks_device']
 
     def device_count(self):
         return int(self.lib.pmg_device_count())
@@ -178,6 +181,8 @@ class PmgLibrary:
         L.pmg_td3_target_work_floats.restype = C.c_int64
         L.pmg_sac_target_work_floats.restype = C.c_int64
         L.pmg_sac_policy_grad_work_floats.restype = C.c_int64
+        L.pmg_mlp_param_floats.restype = C.c_int64
+        L.pmg_mlp_allreduce_work_floats.restype = C.c_int64
 
     def error(self, handle=None):
         msg = self.lib.pmg_last_error(handle)
@@ -569,6 +574,57 @@ class PmgHandle:
     def mlp_polyak_device(self, source, target, tau):
         """target = fmaf(tau, source - target, target) per parameter; stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_mlp_polyak_device(self.h, C.byref(source), C.byref(target), C.c_float(tau)))
+
+    # -- data-parallel learner: rank-ordered gradient and normaliser merge (include/pmg.h, DESIGN.md 3.17) --
+    def comm_info(self):
+        """(rank, nranks) of comm_init(); PmgError before it"""
+        rank, nranks = C.c_int32(), C.c_int32()
+        self._check(self.L.lib.pmg_comm_info(self.h, C.byref(rank), C.byref(nranks)))
+        return rank.value, nranks.value
+
+    def allgather_device(self, d_src_ptr, count, d_gathered_ptr):
+        """count floats of every rank into d_gathered [nranks * count], rank order; a collective, stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_allgather_device(self.h, C.c_void_p(d_src_ptr), C.c_int64(count), C.c_void_p(d_gathered_ptr)))
+
+    def mlp_param_floats(self, shape):
+        """P: the floats of a network's tensors in their flat order, weight 0, bias 0, weight 1, ... (< 0: invalid network)"""
+        return int(self.L.lib.pmg_mlp_param_floats(C.byref(shape)))
+
+    def mlp_params_pack_device(self, shape, src, d_flat_ptr):
+        """the tensors of `src` (a params_struct()) into one flat run of P floats; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_params_pack_device(self.h, C.byref(shape), C.byref(src), C.c_void_p(d_flat_ptr)))
+
+    def mlp_params_merge_device(self, shape, d_slots_ptr, slot_stride, nslots, out):
+        """out = the flat slots at d_slots + r * slot_stride added in ascending r, in float32; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_params_merge_device(self.h, C.byref(shape), C.c_void_p(d_slots_ptr), C.c_int64(slot_stride), C.c_int64(nslots),
+                                                           C.byref(out)))
+
+    def mlp_adam_merge_device(self, shape, param, d_slots_ptr, slot_stride, nslots, grad_out, m, v, adam):
+        """the same sum handed to mlp_adam_device's step in one sweep; grad_out: a params_struct() that receives the sum, or None."""
+        self._check(self.L.lib.pmg_mlp_adam_merge_device(self.h, C.byref(shape), C.byref(param), C.c_void_p(d_slots_ptr), C.c_int64(slot_stride),
+                                                         C.c_int64(nslots), C.byref(grad_out) if grad_out is not None else None, C.byref(m), C.byref(v),
+                                                         C.byref(adam)))
+
+    def mlp_allreduce_work_floats(self, shape):
+        """floats of workspace the two all-reduce calls need: (nranks + 1) * P (< 0: invalid network)"""
+        return int(self.L.lib.pmg_mlp_allreduce_work_floats(self.h, C.byref(shape)))
+
+    def mlp_grad_allreduce_device(self, shape, grads, d_work_ptr, work_floats):
+        """grads = the ranks' grads added in rank order, in place; a collective, stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_mlp_grad_allreduce_device(self.h, C.byref(shape), C.byref(grads), C.c_void_p(d_work_ptr), C.c_int64(work_floats)))
+
+    def mlp_adam_allreduce_device(self, shape, param, grads, m, v, adam, d_work_ptr, work_floats):
+        """one Adam step on `param` with the ranks' grads added in rank order; grads keeps this rank's own; a collective, no host sync."""
+        self._check(self.L.lib.pmg_mlp_adam_allreduce_device(self.h, C.byref(shape), C.byref(param), C.byref(grads), C.byref(m), C.byref(v), C.byref(adam),
+                                                             C.c_void_p(d_work_ptr), C.c_int64(work_floats)))
+
+    def norm_update_ranks_device(self, which, d_rows_ptr, row_stride, batch_local, d_mask_ptr=None):
+        """norm_update_device of the ranks' rows concatenated in rank order, the same totals on every rank; a collective, no host sync."""
+        self._check(self.L.lib.pmg_norm_update_ranks_device(self.h, C.c_int(which), C.c_void_p(d_rows_ptr), C.c_int64(row_stride), C.c_int64(batch_local),
+                                                            C.c_void_p(d_mask_ptr) if d_mask_ptr else None))
+
+    def norm_update_env_ranks_device(self, d_mask_ptr=None):
+        self._check(self.L.lib.pmg_norm_update_env_ranks_device(self.h, C.c_void_p(d_mask_ptr) if d_mask_ptr else None))
 
     def timing_reset(self):
         self._check(self.L.lib.pmg_timing_reset(self.h))

@@ -151,6 +151,7 @@ struct pmg_env {
     struct Norm { int D = 0; double* tot = nullptr; double* part = nullptr; float* der = nullptr; } norm[3];
     float norm_eps = 0.01f, norm_clip_in = 200.f, norm_clip_out = 5.f;
     Scratch her_idx;                  /* e, t, f of a pmg_her_sample_device batch whose caller passed no d_index: kept until a larger batch */
+    Scratch norm_gather;              /* the partial rows of all ranks of a collective normaliser update, [nranks][parts][2 D + 1] doubles: first use */
     char err[512] = "";
 };
 
@@ -538,7 +539,7 @@ void pmg_destroy(pmg_env* e)
     (void)hipFree(e->P.sched); (void)hipFree(e->P.env_cycles); (void)hipFree(e->P.lpt_state);
     (void)hipFree(e->d_actions); (void)hipFree(e->d_mask);
     for (int w = 0; w < 3; w++) (void)hipFree(e->norm[w].tot);
-    for (Scratch* b : {&e->st_a, &e->st_b, &e->st_out, &e->st_flag, &e->her_idx}) b->release();
+    for (Scratch* b : {&e->st_a, &e->st_b, &e->st_out, &e->st_flag, &e->her_idx, &e->norm_gather}) b->release();
     if (e->h_packed) (void)hipHostFree(e->h_packed);
     if (e->h_actions) (void)hipHostFree(e->h_actions);
     for (int i = 0; i < EVENT_POOL; i++) { if (e->ev_a[i]) (void)hipEventDestroy(e->ev_a[i]); if (e->ev_b[i]) (void)hipEventDestroy(e->ev_b[i]); }
@@ -1387,6 +1388,21 @@ static void segs_of(const PmgMlp& M, const pmg_mlp_params* p, const float* const
         }
 }
 
+/* Adam's settings of `who`'s caller, validated -> the device's constants (include/pmg.h); 0 or PMG_E_INVALID */
+static int adam_of(pmg_env* e, const char* who, const pmg_adam* a, PmgAdam& A)
+{
+    if (!a) return fail(e, PMG_E_INVALID, "%s: a is null", who);
+    if (a->struct_size != (int32_t)sizeof(pmg_adam)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, a->struct_size, sizeof(pmg_adam));
+    if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !(a->eps >= 0.f)) return fail(e, PMG_E_INVALID, "%s: lr %g must be finite, eps %g finite and >= 0", who, (double)a->lr, (double)a->eps);
+    if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return fail(e, PMG_E_INVALID, "%s: betas %g / %g must lie in [0, 1)", who, (double)a->beta1, (double)a->beta2);
+    if (a->step < 1) return fail(e, PMG_E_INVALID, "%s: step %lld must be >= 1", who, (long long)a->step);
+    const double c1 = 1.0 - pow((double)a->beta1, (double)a->step), c2 = 1.0 - pow((double)a->beta2, (double)a->step);
+    A.beta1 = a->beta1; A.beta2 = a->beta2;
+    A.omb1 = (float)(1.0 - (double)a->beta1); A.omb2 = (float)(1.0 - (double)a->beta2);
+    A.step_size = (float)((double)a->lr / c1); A.rsc2 = (float)(1.0 / sqrt(c2)); A.eps = a->eps;
+    return PMG_OK;
+}
+
 int pmg_mlp_adam_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grad, const pmg_mlp_params* m,
                         const pmg_mlp_params* v, const pmg_adam* a)
 {
@@ -1398,17 +1414,9 @@ int pmg_mlp_adam_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* 
     if (int rc = params_of(e, M, grad, true, who, "grad")) return rc;
     if (int rc = params_of(e, M, m, true, who, "m")) return rc;
     if (int rc = params_of(e, M, v, true, who, "v")) return rc;
-    if (!a) return fail(e, PMG_E_INVALID, "%s: a is null", who);
-    if (a->struct_size != (int32_t)sizeof(pmg_adam)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, a->struct_size, sizeof(pmg_adam));
-    if (!std::isfinite(a->lr) || !std::isfinite(a->eps) || !(a->eps >= 0.f)) return fail(e, PMG_E_INVALID, "%s: lr %g must be finite, eps %g finite and >= 0", who, (double)a->lr, (double)a->eps);
-    if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f)) return fail(e, PMG_E_INVALID, "%s: betas %g / %g must lie in [0, 1)", who, (double)a->beta1, (double)a->beta2);
-    if (a->step < 1) return fail(e, PMG_E_INVALID, "%s: step %lld must be >= 1", who, (long long)a->step);
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
-    const double c1 = 1.0 - pow((double)a->beta1, (double)a->step), c2 = 1.0 - pow((double)a->beta2, (double)a->step);
     PmgAdam A;
-    A.beta1 = a->beta1; A.beta2 = a->beta2;
-    A.omb1 = (float)(1.0 - (double)a->beta1); A.omb2 = (float)(1.0 - (double)a->beta2);
-    A.step_size = (float)((double)a->lr / c1); A.rsc2 = (float)(1.0 / sqrt(c2)); A.eps = a->eps;
+    if (int rc = adam_of(e, who, a, A)) return rc;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
     PmgSegs T;
     segs_of(M, param, grad->d_weight, grad->d_bias, m, v, T);
     HIP_TRY(e, pmg_launch_adam(T, A, e->stream));
@@ -1854,6 +1862,239 @@ int pmg_allgather_packed(pmg_env* e, float* d_gathered)
     if (rc != ncclSuccess) return fail(e, PMG_E_COMM, "ncclAllGather -> %s", ncclGetErrorString(rc));
     HIP_TRY(e, hipEventRecord(e->cv_b[i], e->stream));
     e->cv_n = i + 1;
+    return PMG_OK;
+}
+
+/* ---- data-parallel learner: rank-ordered gradient and normaliser merge ---- */
+/* a collective on the handle's stream needs the communicator and must be the only stream that uses it */
+static int collective_of(pmg_env* e, const char* who)
+{
+    if (!e->comm) return fail(e, PMG_E_STATE, "%s: pmg_comm_init was not called", who);
+    if (e->overlap) return fail(e, PMG_E_STATE, "%s: pmg_comm_overlap is enabled -- its all-gathers run on the communication stream, and two streams must not "
+                                                "issue collectives on one communicator; switch it off first", who);
+    return PMG_OK;
+}
+static int allgather_floats(pmg_env* e, const char* who, const float* src, size_t count, float* dst)
+{
+    ncclResult_t rc = ncclAllGather(src, dst, count, ncclFloat, e->comm, e->stream);
+    if (rc != ncclSuccess) return fail(e, PMG_E_COMM, "%s: ncclAllGather of %zu floats per rank -> %s", who, count, ncclGetErrorString(rc));
+    return PMG_OK;
+}
+
+int pmg_comm_info(pmg_env* e, int32_t* rank, int32_t* nranks)
+{
+    if (!e) return PMG_E_INVALID;
+    if (!e->comm) return fail(e, PMG_E_STATE, "pmg_comm_info: pmg_comm_init was not called");
+    if (rank) *rank = e->rank;
+    if (nranks) *nranks = e->nranks;
+    return PMG_OK;
+}
+
+int pmg_allgather_device(pmg_env* e, const float* d_src, int64_t count, float* d_gathered)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_allgather_device";
+    if (int rc = collective_of(e, who)) return rc;
+    if (count < 0 || count > (int64_t)1 << 40) return fail(e, PMG_E_INVALID, "%s: count %lld is negative or too large", who, (long long)count);
+    if (!d_src || !d_gathered || ((((size_t)d_src | (size_t)d_gathered) & 3) != 0)) return fail(e, PMG_E_INVALID, "%s: a pointer is null or not aligned to 4 bytes", who);
+    if (count == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return allgather_floats(e, who, d_src, (size_t)count, d_gathered);
+}
+
+/* P of a validated network: the tensors the shape has, in the flat order of PmgSegs */
+static long long param_floats_of(const PmgMlp& M)
+{
+    long long P = 0;
+    for (int l = 0; l < M.L; l++) P += (long long)M.width[l + 1] * M.width[l] + (M.b[l] ? M.width[l + 1] : 0);
+    return P;
+}
+int64_t pmg_mlp_param_floats(const pmg_mlp* shape)
+{
+    PmgMlp M;
+    if (mlp_of(nullptr, shape, "pmg_mlp_param_floats", M) != PMG_OK) return -1;
+    return param_floats_of(M);
+}
+/* nslots slots of P floats, slot_stride apart */
+static int slots_of(pmg_env* e, const char* who, const float* d_slots, int64_t slot_stride, int64_t nslots, long long P)
+{
+    if (!d_slots || ((size_t)d_slots & 3) != 0) return fail(e, PMG_E_INVALID, "%s: d_slots is null or not aligned to 4 bytes", who);
+    if (nslots < 1 || nslots > INT32_MAX) return fail(e, PMG_E_INVALID, "%s: nslots %lld must be >= 1", who, (long long)nslots);
+    if (slot_stride < P) return fail(e, PMG_E_INVALID, "%s: slot_stride %lld is smaller than the %lld parameters of the network", who, (long long)slot_stride, P);
+    return PMG_OK;
+}
+
+int pmg_mlp_params_pack_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* src, float* d_flat)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_params_pack_device";
+    PmgMlp M;
+    if (int rc = mlp_of(e, shape, who, M)) return rc;
+    if (int rc = params_of(e, M, src, true, who, "src")) return rc;
+    if (!d_flat || ((size_t)d_flat & 3) != 0) return fail(e, PMG_E_INVALID, "%s: d_flat is null or not aligned to 4 bytes", who);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgSegs T;
+    segs_of(M, src, src->d_weight, src->d_bias, nullptr, nullptr, T);
+    HIP_TRY(e, pmg_launch_params_pack(T, d_flat, e->stream));
+    return PMG_OK;
+}
+
+int pmg_mlp_params_merge_device(pmg_env* e, const pmg_mlp* shape, const float* d_slots, int64_t slot_stride, int64_t nslots, const pmg_mlp_params* out)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_params_merge_device";
+    PmgMlp M;
+    if (int rc = mlp_of(e, shape, who, M)) return rc;
+    if (int rc = params_of(e, M, out, true, who, "out")) return rc;
+    if (int rc = slots_of(e, who, d_slots, slot_stride, nslots, param_floats_of(M))) return rc;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgSegs T;
+    segs_of(M, out, out->d_weight, out->d_bias, nullptr, nullptr, T);
+    HIP_TRY(e, pmg_launch_params_merge_ranks(T, d_slots, slot_stride, (int)nslots, e->stream));
+    return PMG_OK;
+}
+
+/* everything pmg_mlp_adam_merge_device checks but the slots -> M, A and the table (T.g: grad_out's tensors, or param's when there is none) */
+static int adam_merge_of(pmg_env* e, const char* who, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grad_out,
+                         const pmg_mlp_params* m, const pmg_mlp_params* v, const pmg_adam* a, PmgMlp& M, PmgAdam& A, PmgSegs& T)
+{
+    if (int rc = mlp_of(e, shape, who, M)) return rc;
+    if (int rc = params_of(e, M, param, true, who, "param")) return rc;
+    if (grad_out) if (int rc = params_of(e, M, grad_out, true, who, "grad_out")) return rc;
+    if (int rc = params_of(e, M, m, true, who, "m")) return rc;
+    if (int rc = params_of(e, M, v, true, who, "v")) return rc;
+    if (int rc = adam_of(e, who, a, A)) return rc;
+    const pmg_mlp_params* g = grad_out ? grad_out : param;
+    segs_of(M, param, g->d_weight, g->d_bias, m, v, T);
+    return PMG_OK;
+}
+
+int pmg_mlp_adam_merge_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* param, const float* d_slots, int64_t slot_stride, int64_t nslots,
+                              const pmg_mlp_params* grad_out, const pmg_mlp_params* m, const pmg_mlp_params* v, const pmg_adam* a)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_adam_merge_device";
+    PmgMlp M; PmgAdam A; PmgSegs T;
+    if (int rc = adam_merge_of(e, who, shape, param, grad_out, m, v, a, M, A, T)) return rc;
+    if (int rc = slots_of(e, who, d_slots, slot_stride, nslots, param_floats_of(M))) return rc;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, pmg_launch_adam_merge_ranks(T, A, d_slots, slot_stride, (int)nslots, grad_out ? 1 : 0, e->stream));
+    return PMG_OK;
+}
+
+int64_t pmg_mlp_allreduce_work_floats(const pmg_env* e, const pmg_mlp* shape)
+{
+    const int64_t P = pmg_mlp_param_floats(shape);
+    if (!e || P < 0) return -1;
+    return ((int64_t)e->nranks + 1) * P;
+}
+/* the workspace of an all-reduce: this rank's flat gradient in front, the nranks gathered slots behind it */
+static int allreduce_work_of(pmg_env* e, const char* who, long long P, const float* d_work, int64_t work_floats)
+{
+    const long long need = ((long long)e->nranks + 1) * P;
+    if (!d_work || ((size_t)d_work & 3) != 0 || work_floats < need)
+        return fail(e, PMG_E_INVALID, "%s: d_work is null or not aligned to 4 bytes, or work_floats %lld < %lld", who, (long long)work_floats, need);
+    return PMG_OK;
+}
+
+int pmg_mlp_grad_allreduce_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* grads, float* d_work, int64_t work_floats)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_grad_allreduce_device";
+    if (int rc = collective_of(e, who)) return rc;
+    PmgMlp M;
+    if (int rc = mlp_of(e, shape, who, M)) return rc;
+    if (int rc = params_of(e, M, grads, true, who, "grads")) return rc;
+    const long long P = param_floats_of(M);
+    if (int rc = allreduce_work_of(e, who, P, d_work, work_floats)) return rc;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgSegs T;
+    segs_of(M, grads, grads->d_weight, grads->d_bias, nullptr, nullptr, T);
+    HIP_TRY(e, pmg_launch_params_pack(T, d_work, e->stream));
+    if (int rc = allgather_floats(e, who, d_work, (size_t)P, d_work + P)) return rc;
+    HIP_TRY(e, pmg_launch_params_merge_ranks(T, d_work + P, P, e->nranks, e->stream));
+    return PMG_OK;
+}
+
+int pmg_mlp_adam_allreduce_device(pmg_env* e, const pmg_mlp* shape, const pmg_mlp_params* param, const pmg_mlp_params* grads, const pmg_mlp_params* m,
+                                  const pmg_mlp_params* v, const pmg_adam* a, float* d_work, int64_t work_floats)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_mlp_adam_allreduce_device";
+    if (int rc = collective_of(e, who)) return rc;
+    if (!grads) return fail(e, PMG_E_INVALID, "%s: grads is null", who);
+    PmgMlp M; PmgAdam A; PmgSegs T;
+    if (int rc = adam_merge_of(e, who, shape, param, grads, m, v, a, M, A, T)) return rc;
+    const long long P = param_floats_of(M);
+    if (int rc = allreduce_work_of(e, who, P, d_work, work_floats)) return rc;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, pmg_launch_params_pack(T, d_work, e->stream));          /* (T.g: this rank's gradient) */
+    if (int rc = allgather_floats(e, who, d_work, (size_t)P, d_work + P)) return rc;
+    HIP_TRY(e, pmg_launch_adam_merge_ranks(T, A, d_work + P, P, e->nranks, 0, e->stream));   /* grads keep this rank's own gradient */
+    return PMG_OK;
+}
+
+/* one normaliser's collective update: this rank's partial rows, cut at the chunk of the GLOBAL batch, all ranks' rows gathered in rank order --
+ * the partial rows of the unsharded update in index order --, then the unchanged merge */
+static int norm_update_ranks_rows(pmg_env* e, const char* who, int which, const float* d_rows, int64_t row_stride, int64_t batch, long long chunk,
+                                  const uint8_t* d_mask)
+{
+    pmg_env::Norm& nm = e->norm[which];
+    const size_t P = 2 * (size_t)nm.D + 1;
+    const int parts = (int)((batch + chunk - 1) / chunk);
+    HIP_TRY(e, pmg_launch_norm_partial(d_rows, row_stride, batch, nm.D, chunk, 0, parts, d_mask, e->norm_clip_in, nm.part, e->stream));
+    if (int rc = allgather_floats(e, who, (const float*)nm.part, 2 * P * (size_t)parts, e->norm_gather.f32())) return rc;
+    HIP_TRY(e, pmg_launch_norm_merge((const double*)e->norm_gather.p, e->nranks * parts, nm.D, e->norm_eps, nm.tot, nm.der, e->stream));
+    return PMG_OK;
+}
+/* the chunk of a collective update of batch_local rows per rank, checked; the gathered-partials buffer sized for rows of width D */
+static int norm_ranks_of(pmg_env* e, const char* who, int64_t batch_local, int D, long long& chunk)
+{
+    if (batch_local > (int64_t)1 << 40) return fail(e, PMG_E_INVALID, "%s: batch_local %lld is too large", who, (long long)batch_local);
+    chunk = pmg_norm_chunk((long long)e->nranks * batch_local);
+    if (e->nranks > 1 && batch_local % chunk != 0)
+        return fail(e, PMG_E_INVALID, "%s: batch_local %lld is no multiple of %lld, the chunk of the global batch of %d x %lld rows: a rank's rows must "
+                                      "start and end on chunk boundaries", who, (long long)batch_local, chunk, e->nranks, (long long)batch_local);
+    const size_t parts = (size_t)((batch_local + chunk - 1) / chunk);
+    return e->norm_gather.reserve(e, (size_t)e->nranks * parts * (2 * (size_t)D + 1) * sizeof(double), who, "the gathered partial rows");
+}
+
+int pmg_norm_update_ranks_device(pmg_env* e, int which, const float* d_rows, int64_t row_stride, int64_t batch_local, const uint8_t* d_mask)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_norm_update_ranks_device";
+    if (int rc = collective_of(e, who)) return rc;
+    const pmg_env::Norm* nm = norm_of(e, which, who); if (!nm) return PMG_E_INVALID;
+    if (!d_rows || ((size_t)d_rows & 3) != 0) return fail(e, PMG_E_INVALID, "%s: d_rows is null or not aligned to 4 bytes", who);
+    if (batch_local < 0) return fail(e, PMG_E_INVALID, "%s: batch_local %lld is negative", who, (long long)batch_local);
+    if (row_stride < nm->D) return fail(e, PMG_E_INVALID, "%s: row_stride %lld is smaller than the width %d", who, (long long)row_stride, nm->D);
+    if (nm->D > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "%s: width %d beyond %d", who, nm->D, PMG_NORM_MAX_D);
+    if (batch_local == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    long long chunk;
+    if (int rc = norm_ranks_of(e, who, batch_local, nm->D, chunk)) return rc;
+    return norm_update_ranks_rows(e, who, which, d_rows, row_stride, batch_local, chunk, d_mask);
+}
+
+int pmg_norm_update_env_ranks_device(pmg_env* e, const uint8_t* d_mask)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_norm_update_env_ranks_device";
+    if (int rc = collective_of(e, who)) return rc;
+    if (!e->ever_reset) return fail(e, PMG_E_STATE, "%s: reset() must be called (for all envs) first", who);
+    const pmg_dims& d = e->dims;
+    if ((long long)e->cfg.env_index_offset != (long long)e->rank * d.num_envs)
+        return fail(e, PMG_E_INVALID, "%s: env_index_offset %d is not rank %d x num_envs %d: the ranks' envs must be the global envs in rank order", who,
+                    e->cfg.env_index_offset, e->rank, d.num_envs);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    long long chunk;
+    const int widest = std::max(d.observation_dim, std::max(d.policy_state_dim, d.goal_dim));
+    if (widest > PMG_NORM_MAX_D) return fail(e, PMG_E_INVALID, "%s: width %d beyond %d", who, widest, PMG_NORM_MAX_D);
+    if (int rc = norm_ranks_of(e, who, d.num_envs, widest, chunk)) return rc;
+    const float* rows = e->P.out;
+    const int off[3] = {0, d.observation_dim, d.observation_dim + d.policy_state_dim + d.goal_dim};   /* observation, policy_state, desired_goal */
+    for (int w = 0; w < 3; w++)
+        if (int rc = norm_update_ranks_rows(e, who, w, rows + off[w], d.packed_dim, d.num_envs, chunk, d_mask)) return rc;
     return PMG_OK;
 }
 

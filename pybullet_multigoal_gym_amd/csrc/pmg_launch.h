@@ -25,6 +25,13 @@ hipError_t pmg_launch_norm_update(const float* d_rows, long long row_stride, lon
                                   const unsigned char* d_mask, float clip_input, float eps, double* part, double* tot,
                                   float* der, hipStream_t s);
 hipError_t pmg_launch_norm_derive(int D, float eps, double* tot, float* der, hipStream_t s);
+/* the halves of pmg_launch_norm_update for a collective update: pmg_norm_chunk(B) = the chunk pmg_launch_norm_update cuts a
+ * batch of B rows into; pmg_launch_norm_partial writes the nparts partial rows of B local rows cut at `chunk` (lead = row0 % chunk) to part;
+ * pmg_launch_norm_merge adds nparts partial rows in index order onto tot and re-derives der */
+long long pmg_norm_chunk(long long B);
+hipError_t pmg_launch_norm_partial(const float* d_rows, long long row_stride, long long B, int D, long long chunk, long long lead, int nparts,
+                                   const unsigned char* d_mask, float clip_input, double* part, hipStream_t s);
+hipError_t pmg_launch_norm_merge(const double* part, int nparts, int D, float eps, double* tot, float* der, hipStream_t s);
 /* out[B, Ds + Dg] = clip((clip(v) - mean) * inv_std) of state | goal rows; der_* = the derived arrays of their normalisers */
 hipError_t pmg_launch_policy_input(const float* d_state, long long state_stride, int Ds, const float* d_goal, long long goal_stride,
                                    int Dg, long long B, const float* der_state, const float* der_goal, float clip_input,
@@ -200,4 +207,11 @@ struct PmgSacAlpha {
 hipError_t pmg_launch_sac_alpha(const PmgSacAlpha& X, hipStream_t s);
 hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
+/* the data-parallel merge (pmg_mlp_params_pack_device, pmg_mlp_params_merge_device, pmg_mlp_adam_merge_device), validated by
+ * the caller.  flat / a slot: the tensors of T in its flat order, T.end[T.n - 1] floats.  pack: T.g -> flat.  merge: the nslots >= 1 slots at
+ * slots + r * stride added in ascending r -> T.p.  adam_merge: the same sum as the gradient of pmg_launch_adam's step on T.p / T.m / T.v;
+ * keep != 0: the sum is also written to the tensors T.g names. */
+hipError_t pmg_launch_params_pack(const PmgSegs& T, float* flat, hipStream_t s);
+hipError_t pmg_launch_params_merge_ranks(const PmgSegs& T, const float* slots, long long stride, int nslots, hipStream_t s);
+hipError_t pmg_launch_adam_merge_ranks(const PmgSegs& T, const PmgAdam& A, const float* slots, long long stride, int nslots, int keep, hipStream_t s);
 #endif

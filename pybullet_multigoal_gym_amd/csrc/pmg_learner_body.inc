@@ -234,6 +234,22 @@ hipError_t pmg_launch_norm_update(const float* d_rows, long long row_stride, lon
     hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, (const double*)part, nparts, D, tot, der, eps);
     return hipGetLastError();
 }
+/* the two halves on their own, for an update whose partial rows cross ranks between them (pmg_norm_update_ranks_device, DESIGN.md 3.17): the
+ * caller supplies the chunk -- that of the GLOBAL batch -- and merges the gathered rows of all ranks */
+long long pmg_norm_chunk(long long B) { return norm_chunk(B); }
+hipError_t pmg_launch_norm_partial(const float* d_rows, long long row_stride, long long B, int D, long long chunk, long long lead, int nparts,
+                                   const unsigned char* d_mask, float clip_input, double* part, hipStream_t s)
+{
+    int W = 1;
+    while (W < D) W <<= 1;
+    hipLaunchKernelGGL(pmg_k_norm_partial, dim3(nparts), dim3(256), 0, s, d_rows, row_stride, B, D, W, chunk, lead, d_mask, clip_input, part);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_norm_merge(const double* part, int nparts, int D, float eps, double* tot, float* der, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_norm_merge, dim3(1), dim3(256), 0, s, part, nparts, D, tot, der, eps);
+    return hipGetLastError();
+}
 
 /* Policy-input rows out[B, Ds + Dg] = clip((clip(v, clip_in) - mean) * inv_std, clip_out) of state | goal rows.  HBM-bound like the
  * reward kernels above: 4 bytes in and 4 bytes out per element, each touched once.  flat_sweep: an output is ONE flat stream of
@@ -1330,6 +1346,67 @@ hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s)
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s)
 {
     hipLaunchKernelGGL(pmg_k_polyak, dim3(seg_grid(T)), dim3(256), 0, s, T, tau);
+    return hipGetLastError();
+}
+
+/* The data-parallel merge (pmg_mlp_params_pack_device, pmg_mlp_params_merge_device, pmg_mlp_adam_merge_device, DESIGN.md 3.17): three
+ * elementwise sweeps of the shape of pmg_k_adam -- a thread per parameter, consecutive addresses across the lanes on the flat side, the
+ * tensor of a flat element found by seg_at, dword accesses (the tensors come with any 4-byte alignment).  A slot is one rank's gradient in
+ * the flat order of PmgSegs; slot r starts at slots + r * stride.  The sum is G_0 + G_1 + ... in ascending r from G_0 ITSELF, one float32
+ * rounding per addition: no atomics, nothing depends on the grid. */
+__global__ void __launch_bounds__(256) pmg_k_params_pack(PmgSegs T, float* __restrict__ flat)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const SegAt s = seg_at(T, i);
+        flat[i] = s.g[s.i];
+    }
+}
+__device__ __forceinline__ float rank_sum(const float* __restrict__ slots, long long stride, int n, long long i)
+{
+    const float* __restrict__ p = slots + i;
+    float acc = p[0];
+#pragma unroll 8
+    for (int r = 1; r < n; r++) acc = acc + p[(long long)r * stride];
+    return acc;
+}
+__global__ void __launch_bounds__(256) pmg_k_params_merge_ranks(PmgSegs T, const float* __restrict__ slots, long long stride, int n)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const float acc = rank_sum(slots, stride, n, i);
+        const SegAt s = seg_at(T, i);
+        s.p[s.i] = acc;
+    }
+}
+/* the same sum handed straight to pmg_k_adam's step: the summed gradient stays in a register; keep != 0: it is also stored to the tensors of
+ * T.g (the caller's grad_out, writable: the table merely types them as the gradient pmg_k_adam reads) */
+__global__ void __launch_bounds__(256) pmg_k_adam_merge_ranks(PmgSegs T, PmgAdam A, const float* __restrict__ slots, long long stride, int n, int keep)
+{
+    const long long total = T.end[T.n - 1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const float g = rank_sum(slots, stride, n, i);
+        const SegAt s = seg_at(T, i);
+        if (keep) const_cast<float*>(s.g)[s.i] = g;
+        const float m = fmaf(A.beta1, s.m[s.i], A.omb1 * g);
+        const float v = fmaf(A.beta2, s.v[s.i], A.omb2 * (g * g));
+        s.m[s.i] = m; s.v[s.i] = v;
+        s.p[s.i] = s.p[s.i] - A.step_size * (m / (sqrtf(v) * A.rsc2 + A.eps));
+    }
+}
+hipError_t pmg_launch_params_pack(const PmgSegs& T, float* flat, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_params_pack, dim3(seg_grid(T)), dim3(256), 0, s, T, flat);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_params_merge_ranks(const PmgSegs& T, const float* slots, long long stride, int nslots, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_params_merge_ranks, dim3(seg_grid(T)), dim3(256), 0, s, T, slots, stride, nslots);
+    return hipGetLastError();
+}
+hipError_t pmg_launch_adam_merge_ranks(const PmgSegs& T, const PmgAdam& A, const float* slots, long long stride, int nslots, int keep, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_adam_merge_ranks, dim3(seg_grid(T)), dim3(256), 0, s, T, A, slots, stride, nslots, keep);
     return hipGetLastError();
 }
 

@@ -391,6 +391,29 @@ def init_rccl(env, rdv, _force_fail=False):
     return rdv.min(ok) == 1
 
 
+def check_data_parallel(env, rdv, batch_local=None):
+    """What the collectives of a data-parallel learner assume, checked once before the first update: the handle has its
+    communicator with the rendezvous' rank and world size, every rank holds the same number of envs (and of minibatch rows, when
+    ``batch_local`` is given, an even number), and this rank's envs are the global envs rank * N ... rank * N + N - 1.  Raises ValueError
+    with the reason on every rank otherwise; -> (rank, nranks)."""
+    h = env.handle
+    rank, nranks = h.comm_info()
+    why = None
+    if (rank, nranks) != (rdv.rank, rdv.world):
+        why = 'the communicator says rank %d of %d, the rendezvous rank %d of %d' % (rank, nranks, rdv.rank, rdv.world)
+    elif h.cfg.env_index_offset != rank * h.N:
+        why = 'env_index_offset %d is not rank %d x num_envs %d (make_sharded_env gives that layout)' % (h.cfg.env_index_offset, rank, h.N)
+    elif batch_local is not None and (batch_local < 2 or batch_local % 2):
+        why = 'batch_local %r must be an even number of rows' % (batch_local,)
+    seen = rdv.allgather([int(h.N), -1 if batch_local is None else int(batch_local), why or ''])
+    if any(s[:2] != seen[0][:2] for s in seen):
+        why = why or 'unequal shards: (num_envs, batch_local) per rank = %s' % [tuple(s[:2]) for s in seen]
+    whys = ['rank %d: %s' % (r, s[2]) for r, s in enumerate(seen) if s[2]]
+    if why or whys:
+        raise ValueError('not a data-parallel layout: ' + '; '.join(whys or [why]))
+    return rank, nranks
+
+
 def pack_outputs(env, obs, reward, done, goal_achieved):
     """Host-side row layout of PMG_BUF_PACKED: obs | policy | ag | dg | reward | goal_achieved | done."""
     n = env.num_envs

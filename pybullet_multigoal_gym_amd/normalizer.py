@@ -63,6 +63,48 @@ class Normalizer:
         finally:
             h.device_free(d_mask)   # waits for the handle's stream first
 
+    def update_ranks(self, observation=None, policy_state=None, goal=None, mask=None):
+        """``update`` as a collective of a data-parallel learner: every rank passes ITS rows -- the same number on every rank,
+        rank r's rows being rows r * B_local ... of the global batch -- and every rank ends with the totals of ONE ``update`` on the
+        concatenated rows, bit for bit.  With more than one rank B_local must be a multiple of the chunk of the global batch,
+        64 * ceil(R * B_local / 65 408).  Every rank must make the same calls; needs ``comm_init`` and no ``comm_overlap``."""
+        h = self._h
+        given = [(KINDS[k], self._rows(v, KINDS[k])) for k, v in
+                 (('observation', observation), ('policy_state', policy_state), ('goal', goal)) if v is not None]
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        for which, rows in given:
+            if m is not None and m.shape[0] != rows.shape[0]:
+                raise ValueError('mask has %d entries for %d rows' % (m.shape[0], rows.shape[0]))
+            ptrs = []
+            try:
+                ptrs.append(h.device_alloc(max(rows.nbytes, 4)))
+                h.upload(ptrs[0], rows)
+                if m is not None:
+                    ptrs.append(h.device_alloc(max(m.nbytes, 4)))
+                    h.upload(ptrs[1], m)
+                h.norm_update_ranks_device(which, ptrs[0], rows.shape[1], rows.shape[0], ptrs[1] if m is not None else None)
+                h.sync()
+            finally:
+                for p in ptrs:
+                    h.device_free(p)
+
+    def update_from_env_ranks(self, mask=None):
+        """``update_from_env`` as a collective: the rows of every rank's envs, the totals of one unsharded env of all of them on every rank.
+        The ranks' envs must be the global envs in rank order (``distributed.check_data_parallel``)."""
+        h = self._h
+        if mask is None:
+            h.norm_update_env_ranks_device(None)
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(h.N)
+        d_mask = h.device_alloc(h.N)
+        try:
+            h.upload(d_mask, m)
+            h.norm_update_env_ranks_device(d_mask)
+        finally:
+            h.device_free(d_mask)   # waits for the handle's stream first
+
     def policy_input(self, state, goal, kind='policy_state'):
         """[..., Ds + Dg] float32: clip((clip(v) - mean) * inv_std) of ``state`` (of ``kind``) and ``goal``, side by side."""
         which = self._kind(kind, state_only=True)

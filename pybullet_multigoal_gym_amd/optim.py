@@ -5,6 +5,8 @@ Host-side face of ``pmg_mlp_grad_device``, ``pmg_mlp_grad_chunked_device``, ``pm
 arithmetic happens in the HIP library.  ``Trainable`` is what ``Actor`` and ``Critic`` share: both are networks whose uploaded weights
 the object owns, so both get ``grad_device`` / ``grad`` / ``adam_step_device`` / ``soft_update_from`` from here.  ``ParamBuffers`` is a
 set of device tensors shaped like a network (gradients, Adam's moments); ``AdamState`` owns the two moments, a gradient buffer and t.
+For a data-parallel learner ``Trainable`` also carries the rank-ordered merge of the ranks' gradients:
+``allreduce_grads_device``, ``adam_step_allreduce_device``, ``allreduce_work_floats`` and the numpy faces ``pack_params`` / ``merge_params``.
 """
 import numpy as np
 
@@ -223,19 +225,92 @@ class Trainable:
         """One Adam step on this object's own uploaded weights.  ``grads``: a ParamBuffers (e.g. ``state.g`` after ``grad_device``) or the
         dict ``grad()`` returned (uploaded into ``state.g``).  Advances ``state.t``.  On the handle's stream, no host sync."""
         mlp = self._loaded()
-        if not isinstance(state, AdamState) or state.m is None or state.m.widths != list(self.widths):
-            raise ValueError('state must be an open AdamState of this network')
-        lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
-        if not (np.isfinite(lr) and np.isfinite(eps) and eps >= 0.0 and 0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
-            raise ValueError('lr %r must be finite, eps %r finite and >= 0, the betas %r / %r in [0, 1)' % (lr, eps, beta1, beta2))
+        adam = self._adam_args(state, lr, beta1, beta2, eps)
         if isinstance(grads, dict):
             state.g.upload(grads['dW'], grads['db'])
             grads = state.g
         if not isinstance(grads, ParamBuffers) or grads.widths != list(self.widths):
             raise ValueError('grads must be a ParamBuffers of this network or the dict grad() returns')
-        h = self._h
-        h.mlp_adam_device(mlp, self._own_params(), grads.struct, state.m.struct, state.v.struct, h.adam_struct(lr, state.t + 1, beta1, beta2, eps))
+        self._h.mlp_adam_device(mlp, self._own_params(), grads.struct, state.m.struct, state.v.struct, adam)
         state.t += 1
+
+    # -- data-parallel learner: the rank-ordered merge of gradients (include/pmg.h, DESIGN.md 3.17) --
+    def _grads_of(self, grads):
+        if not isinstance(grads, ParamBuffers) or grads.widths != list(self.widths):
+            raise ValueError('grads must be a ParamBuffers of this network')
+        return grads
+
+    def _adam_args(self, state, lr, beta1, beta2, eps):
+        if not isinstance(state, AdamState) or state.m is None or state.m.widths != list(self.widths):
+            raise ValueError('state must be an open AdamState of this network')
+        lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+        if not (np.isfinite(lr) and np.isfinite(eps) and eps >= 0.0 and 0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+            raise ValueError('lr %r must be finite, eps %r finite and >= 0, the betas %r / %r in [0, 1)' % (lr, eps, beta1, beta2))
+        return self._h.adam_struct(lr, state.t + 1, beta1, beta2, eps)
+
+    def param_floats(self):
+        """P: the floats of this network's tensors in their flat order (weight 0, bias 0, weight 1, ...)"""
+        return self._h.mlp_param_floats(self._loaded())
+
+    def allreduce_work_floats(self):
+        """floats of workspace ``allreduce_grads_device`` / ``adam_step_allreduce_device`` need: (nranks + 1) * P"""
+        return self._h.mlp_allreduce_work_floats(self._loaded())
+
+    def allreduce_grads_device(self, grads, d_work, work_floats):
+        """``grads`` (a ParamBuffers each rank filled with ``grad_device`` on ITS rows, gscale = ... / B_global) becomes the ranks' gradients
+        added in rank order, in place: the bits of ``grad_device(chunk_rows=B_local)`` on the concatenated batch on one GPU, the same on every
+        rank.  A collective on the handle's stream (every rank calls it), no host sync; not while ``comm_overlap`` is on."""
+        self._h.mlp_grad_allreduce_device(self._loaded(), self._grads_of(grads).struct, d_work, int(work_floats))
+
+    def adam_step_allreduce_device(self, grads, state, lr, d_work, work_floats, beta1=0.9, beta2=0.999, eps=1e-8):
+        """``allreduce_grads_device`` and ``adam_step_device`` in one sweep: the summed gradient is never stored; ``grads`` keeps this rank's own.
+        Advances ``state.t``.  A collective on the handle's stream, no host sync."""
+        mlp = self._loaded()
+        adam = self._adam_args(state, lr, beta1, beta2, eps)
+        self._h.mlp_adam_allreduce_device(mlp, self._own_params(), self._grads_of(grads).struct, state.m.struct, state.v.struct, adam, d_work, int(work_floats))
+        state.t += 1
+
+    def _flat(self, flat, rows=None):
+        P = self.param_floats()
+        a = np.ascontiguousarray(flat, np.float32)
+        if (a.ndim != 1 and rows is None) or (rows is not None and a.ndim != 2) or a.shape[-1] != P or a.shape[0] < 1:
+            raise ValueError('expected %s of %d floats, got shape %s' % ('a flat gradient' if rows is None else 'slots [R, P]', P, a.shape))
+        return a
+
+    def pack_params(self, weights, biases=None):
+        """numpy face of pmg_mlp_params_pack_device: the tensors (lists per layer, as ``grad()`` returns dW / db) -> one flat array [P]"""
+        mlp, h = self._loaded(), self._h
+        has_bias = [bool(mlp.d_bias[l]) for l in range(len(self.widths) - 1)]
+        out = np.empty(self.param_floats(), np.float32)
+        bufs, d_flat = ParamBuffers(h, self.widths, has_bias), None
+        try:
+            bufs.upload(weights, biases)
+            d_flat = h.device_alloc(out.nbytes)
+            h.mlp_params_pack_device(mlp, bufs.struct, d_flat)
+            h.sync()
+            h.download(out, d_flat)
+        finally:
+            bufs.close()
+            if d_flat is not None:
+                h.device_free(d_flat)
+        return out
+
+    def merge_params(self, slots):
+        """numpy face of pmg_mlp_params_merge_device: slots [R, P] (row r: rank r's flat gradient) -> (dW, db), lists per layer, the slots
+        added in ascending r in float32"""
+        mlp, h = self._loaded(), self._h
+        slots = self._flat(slots, rows=True)
+        has_bias = [bool(mlp.d_bias[l]) for l in range(len(self.widths) - 1)]
+        bufs, d_slots = ParamBuffers(h, self.widths, has_bias), None
+        try:
+            d_slots = h.device_alloc(slots.nbytes)
+            h.upload(d_slots, slots)
+            h.mlp_params_merge_device(mlp, d_slots, slots.shape[1], slots.shape[0], bufs.struct)
+            return bufs.download()
+        finally:
+            bufs.close()
+            if d_slots is not None:
+                h.device_free(d_slots)
 
     def soft_update_from(self, other, tau):
         """Polyak onto this object's weights: w = fmaf(tau, other's w - w, w).  On the handle's stream, no host sync."""
