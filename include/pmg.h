@@ -467,6 +467,45 @@ typedef struct pmg_policy_grad {
 int64_t pmg_policy_grad_work_floats(const pmg_mlp* actor, const pmg_mlp* critic, int64_t batch, int64_t chunk_rows);   /* chunk_rows 0: one chain; < 0: invalid */
 int pmg_policy_grad_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows);
 
+/* pmg_policy_grad_bc_device (normative), float32 throughout: pmg_policy_grad_device with a behaviour-cloning term on the
+ * demonstration rows of the minibatch and its Q-filter (Nair et al., Overcoming Exploration in RL with Demonstrations; the bc_loss / q_filter
+ * options of OpenAI baselines' HER) -- the gradient of
+ *   gscale * sum_b Q(x[b], clip(pi(x[b]))) + l2scale / 2 * sum_b sum_j pi(x[b])[j]^2 + bcscale / 2 * sum_{b in F} sum_j (pi(x[b])[j] - ad[b][j])^2
+ * with respect to the actor's parameters, F = the demonstration rows that are cloned, a constant of the gradient.  Rows b >= demo_begin are
+ * demonstrations (baselines puts them last) with the demonstrated action ad[b].  baselines' prm_loss_weight * -mean Q + aux_loss_weight *
+ * sum of squares is gscale = -prm_loss_weight / B, bcscale = 2 * aux_loss_weight.  With q_filter == 0 and demo_begin == 0 the head is TD3+BC's
+ * actor loss.  Per row b, steps 1-3 of pmg_policy_grad_device are taken to the letter (o, a = clip(o), q, ga).  Then:
+ *   2b. for b >= demo_begin: qd = critic.out_activation(z), z = the critic's chain on the row x[b] | ad[b] -- ad as given, not clipped --,
+ *       the chain pmg_q_device runs on that row.  d_q_demo[b] receives qd.
+ *   2c. f = b >= demo_begin && (!q_filter || qd > q), a float32 compare: a NaN on either side gives 0, qd == q gives 0.  d_filter[b] receives f.
+ *   4.  g4[j] = fmaf(l2scale, o[j], inside ? ga[j] : +0.0f) as there;  g[j] = f ? fmaf(bcscale, o[j] - ad[b][j], g4[j]) : g4[j].  The
+ *       difference is rounded once, then the fmaf rounds; like the L2 term, the cloning term acts on the unclipped o.
+ *   5.  as there, from g; single chain or chunked.
+ * So the call equals, bit for bit with zeros compared by value, pmg_mlp_forward_device(actor) -> clip on the host -> pmg_q_device on x | ad ->
+ * pmg_mlp_grad_device(critic, x | a, constant head, input gradients only) -> f and g on the host with an exact fmaf ->
+ * pmg_mlp_grad[_chunked]_device(actor, d_gout = g).  With demo_begin == B every output has the bits of pmg_policy_grad_device, d_filter is
+ * all 0, d_q_demo is untouched and d_demo_action may be NULL.  A row's outputs depend on its own x and ad, the weights and on whether
+ * b >= demo_begin -- not on the batch, the grid or the neighbouring rows: a batch cut at row s gives the same rows when each piece passes
+ * clamp(demo_begin - s, 0, B_piece).  dW and db depend on the row order and chunk_rows as there.
+ * Workspace: exactly pmg_policy_grad_work_floats(actor, critic, batch, chunk_rows).  grads == NULL: steps 4 and 5 do not run and d_work is
+ * not touched; d_q_demo and d_filter are still written.
+ * PMG_E_INVALID, with nothing launched: everything pmg_policy_grad_device rejects, d_q_demo and d_filter counting as outputs in its "all
+ * outputs NULL" rule; bc NULL or a wrong struct_size; bcscale not finite; q_filter not 0 / 1; demo_begin outside [0, B]; d_demo_action NULL
+ * while demo_begin < B, or off 4 bytes, or with a stride below A; d_q_demo off 4 bytes.  batch == 0 is a successful no-op. */
+typedef struct pmg_policy_bc {
+    int32_t struct_size;
+    int32_t q_filter;                 /* 0: every demonstration row is cloned; 1: only where q_demo > q */
+    float   bcscale;                  /* finite; the term is bcscale / 2 * sum over cloned rows of sum_j (o[j] - ad[j])^2 */
+    int32_t reserved;
+    int64_t demo_begin;               /* 0 <= demo_begin <= B: rows b >= demo_begin are demonstrations */
+    const float* d_demo_action; int64_t demo_action_stride;   /* [B, A], indexed by the batch row b; rows below demo_begin are never read, so the
+                                                                 sampler's d_action of the joined minibatch can be passed as it is */
+    float*   d_q_demo;                /* [B] or NULL: Q(x[b], ad[b]); written for b >= demo_begin only */
+    uint8_t* d_filter;                /* [B] or NULL, any address: 1 where the row was cloned, 0 elsewhere (every row is written) */
+} pmg_policy_bc;
+int pmg_policy_grad_bc_device(pmg_env* env, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, const pmg_policy_bc* bc,
+                              int64_t chunk_rows);
+
 /* pmg_td3_target_device (normative), float32 throughout: the TD target of TD3 in one call -- target-policy smoothing and the
  * smaller of two target critics,
  *   y = clip(r + gamma * min(Q1'(x', a~), Q2'(x', a~))),   a~ = clip(clip(pi'(x')) + clip(sigma * n, -c, c), -1, 1),   n ~ N(0, 1).

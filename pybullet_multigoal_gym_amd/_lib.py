@@ -108,6 +108,11 @@ class PmgPolicyGrad(C.Structure):
                 ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
 
 
+class PmgPolicyBc(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('q_filter', C.c_int32), ('bcscale', C.c_float), ('reserved', C.c_int32), ('demo_begin', C.c_int64),
+                ('d_demo_action', C.c_void_p), ('demo_action_stride', C.c_int64), ('d_q_demo', C.c_void_p), ('d_filter', C.c_void_p)]
+
+
 class PmgSacPolicyGrad(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gscale', C.c_float), ('lscale', C.c_float), ('alpha', C.c_float), ('ls_lo', C.c_float),
                 ('ls_hi', C.c_float), ('sample', C.c_int32), ('reserved2', C.c_int32), ('seed', C.c_uint64), ('counter', C.c_uint64), ('row_offset', C.c_int64),
@@ -149,6 +154,7 @@ class PmgLibrary:
                'pmg_her_sample_device', 'pmg_device_copy', 'pmg_mlp_forward_device', 'pmg_act_env_device', 'pmg_q_device', 'pmg_td_target_device',
                'pmg_mlp_grad_work_floats', 'pmg_mlp_grad_device', 'pmg_mlp_adam_device', 'pmg_mlp_polyak_device',
                'pmg_mlp_grad_chunked_work_floats', 'pmg_mlp_grad_chunked_device', 'pmg_policy_grad_work_floats', 'pmg_policy_grad_device',
+               'pmg_policy_grad_bc_device',
                'pmg_td3_target_work_floats', 'pmg_td3_target_device',
                'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device',
                'pmg_sac_policy_grad_work_floats', 'pmg_sac_policy_grad_device', 'pmg_sac_alpha_device',
@@ -566,6 +572,15 @@ class PmgHandle:
     def policy_grad_device(self, actor, critic, grad, chunk_rows=0):
         """the actor's gradient through the critic, L2 and clip terms included, of a policy_grad_struct(); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_policy_grad_device(self.h, C.byref(actor), C.byref(critic), C.byref(grad), C.c_int64(chunk_rows)))
+
+    @staticmethod
+    def policy_bc_struct(demo_begin, d_demo_action, demo_action_stride, bcscale, q_filter=1, d_q_demo=None, d_filter=None):
+        """pmg_policy_bc from device pointers (integers or None): rows from demo_begin on are demonstrations with the actions d_demo_action [B, A]."""
+        return PmgPolicyBc(C.sizeof(PmgPolicyBc), int(q_filter), bcscale, 0, demo_begin, d_demo_action, demo_action_stride, d_q_demo, d_filter)
+
+    def policy_grad_bc_device(self, actor, critic, grad, bc, chunk_rows=0):
+        """policy_grad_device with the behaviour-cloning term of a policy_bc_struct() on the demonstration rows; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_policy_grad_bc_device(self.h, C.byref(actor), C.byref(critic), C.byref(grad), C.byref(bc), C.c_int64(chunk_rows)))
 
     def mlp_adam_device(self, shape, param, grad, m, v, adam):
         """one Adam step on the tensors of `param` (params_struct()s, adam_struct()); stream-ordered, no host sync."""

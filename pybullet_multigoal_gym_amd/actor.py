@@ -1,7 +1,8 @@
 """The actor of a goal-conditioned learner on the device: a small MLP and DDPG / HER's exploration on its output.
 
 Host-side face of ``pmg_mlp_forward_device``, ``pmg_act_env_device`` (include/pmg.h) and ``pmg_policy_grad_device``, the
-actor's half of an update through the critic in one call.  All arithmetic happens
+actor's half of an update through the critic in one call, and of ``pmg_policy_grad_bc_device``, the same with a
+behaviour-cloning term and its Q-filter on the demonstration rows of the minibatch.  All arithmetic happens
 in the HIP library; this file uploads the network, validates shapes and moves buffers.  The library keeps no learner state: the
 weights live in buffers this object owns until ``close()`` (or the next ``load``).  A device-resident rollout is two
 stream-ordered calls per step and nothing leaves the GPU:
@@ -204,6 +205,81 @@ class Actor(Trainable):
                 h.device_free(p)
             if bufs is not None:
                 bufs.close()
+        return res
+
+    def policy_grad_bc_device(self, critic, batch, d_x, d_demo_action, demo_begin, d_work, work_floats, gscale, bcscale, l2scale=0.0, q_filter=True,
+                              grads=None, d_action=None, d_out=None, d_q=None, d_gaction=None, d_q_demo=None, d_filter=None, x_stride=None,
+                              demo_action_stride=None, chunk_rows=None):
+        """``policy_grad_device`` with a behaviour-cloning term on the demonstration rows (pmg_policy_grad_bc_device): rows from
+        ``demo_begin`` on are demonstrations with the actions d_demo_action [batch, A] (indexed by the batch row; rows below ``demo_begin`` are not
+        read, None is allowed with ``demo_begin == batch``).  The term ``bcscale / 2 * sum (pi(x) - a_demo)^2`` runs over the demonstration rows
+        -- with ``q_filter`` only over those where the critic rates the demonstrated action above the policy's own.  baselines'
+        ``prm_loss_weight * -mean Q + aux_loss_weight * sum of squares`` is ``gscale = -prm_loss_weight / B``, ``bcscale = 2 * aux_loss_weight``.
+        d_q_demo [batch] floats (written from ``demo_begin`` on) and d_filter [batch] bytes are optional; the workspace is
+        ``policy_grad_work_floats``.  On the handle's stream, no host sync."""
+        mlp, A = self._loaded(), self.widths[-1]
+        cmlp = self._online_critic(critic)
+        chunk_rows = self._chunk_rows(chunk_rows)
+        g = self._h.policy_grad_struct(int(batch), d_x, self.widths[0] if x_stride is None else x_stride, d_work, int(work_floats), float(gscale),
+                                       float(l2scale), None if grads is None else grads.struct, d_action, A, d_out, A, d_q, d_gaction, A)
+        bc = self._h.policy_bc_struct(int(demo_begin), d_demo_action, A if demo_action_stride is None else demo_action_stride, float(bcscale),
+                                      1 if q_filter else 0, d_q_demo, d_filter)
+        self._h.policy_grad_bc_device(mlp, cmlp, g, bc, chunk_rows or 0)
+
+    def policy_grad_bc(self, critic, x, demo_action, demo_begin, gscale, bcscale, l2scale=0.0, q_filter=True, grads=True, chunk_rows=None):
+        """x [B, Dx], demo_action [B, A] (rows below ``demo_begin`` are not read) -> ``policy_grad``'s dict plus q_demo [B] (NaN below
+        ``demo_begin``, where nothing is computed) and filter [B] bool.  The arguments are those of ``policy_grad_bc_device``."""
+        self._loaded()
+        self._online_critic(critic)
+        chunk_rows = self._chunk_rows(chunk_rows)
+        h, Dx, A = self._h, self.widths[0], self.widths[-1]
+        x = np.ascontiguousarray(x, np.float32)
+        demo_action = np.ascontiguousarray(demo_action, np.float32)
+        if x.ndim != 2 or x.shape[1] != Dx:
+            raise ValueError('x %s must be [B, %d]' % (x.shape, Dx))
+        B = x.shape[0]
+        if demo_action.shape != (B, A):
+            raise ValueError('demo_action %s must be [%d, %d]' % (demo_action.shape, B, A))
+        if not np.isfinite(gscale) or not np.isfinite(l2scale) or not np.isfinite(bcscale):
+            raise ValueError('gscale %r, l2scale %r and bcscale %r must be finite' % (gscale, l2scale, bcscale))
+        if int(demo_begin) != demo_begin or not 0 <= demo_begin <= B:
+            raise ValueError('demo_begin %r must be an integer in [0, %d]' % (demo_begin, B))
+        res = {'dW': None, 'db': None, 'action': np.empty((B, A), np.float32), 'out': np.empty((B, A), np.float32), 'q': np.empty(B, np.float32),
+               'gaction': np.empty((B, A), np.float32), 'q_demo': np.full(B, np.nan, np.float32), 'filter': np.zeros(B, np.uint8)}
+        has_bias = [bool(self._mlp.d_bias[l]) for l in range(len(self.widths) - 1)]
+        if B == 0:
+            if grads:
+                res['dW'] = [np.zeros((self.widths[l + 1], self.widths[l]), np.float32) for l in range(len(has_bias))]
+                res['db'] = [np.zeros(self.widths[l + 1], np.float32) if keep else None for l, keep in enumerate(has_bias)]
+            res['filter'] = res['filter'].astype(bool)
+            return res
+        ptrs, bufs = [], None
+        try:
+            def room(arr, fill=False):
+                ptrs.append(h.device_alloc(arr.nbytes))
+                if fill:
+                    h.upload(ptrs[-1], arr)
+                return ptrs[-1]
+            d_x, d_ad = room(x, True), room(demo_action, True)
+            outs = [(res[k], room(res[k], k == 'q_demo')) for k in ('action', 'out', 'q', 'gaction', 'q_demo', 'filter')]
+            work = self.policy_grad_work_floats(critic, B, chunk_rows if grads else None)
+            d_work = h.device_alloc(4 * max(work, 1))
+            ptrs.append(d_work)
+            if grads:
+                bufs = ParamBuffers(h, self.widths, has_bias)
+            self.policy_grad_bc_device(critic, B, d_x, d_ad, int(demo_begin), d_work, work, gscale, bcscale, l2scale, q_filter, bufs, outs[0][1], outs[1][1],
+                                       outs[2][1], outs[3][1], outs[4][1], outs[5][1], chunk_rows=chunk_rows)
+            h.sync()
+            for arr, p in outs:
+                h.download(arr, p)
+            if grads:
+                res['dW'], res['db'] = bufs.download()
+        finally:
+            for p in ptrs:
+                h.device_free(p)
+            if bufs is not None:
+                bufs.close()
+        res['filter'] = res['filter'].astype(bool)
         return res
 
     def close(self):

@@ -1500,13 +1500,14 @@ int64_t pmg_policy_grad_work_floats(const pmg_mlp* actor, const pmg_mlp* critic,
     return pmg_mlp_grad_chunked_work_floats(actor, batch, chunk_rows);
 }
 
-int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows)
+/* pmg_policy_grad_device (with_bc false: bc is not looked at) and pmg_policy_grad_bc_device: one validation, one launch */
+static int policy_grad_call(pmg_env* e, const char* who, const char* who_actor, const char* who_critic, const pmg_mlp* actor, const pmg_mlp* critic,
+                            const pmg_policy_grad* g, bool with_bc, const pmg_policy_bc* bc, int64_t chunk_rows)
 {
     if (!e) return PMG_E_INVALID;
-    const char* who = "pmg_policy_grad_device";
     PmgMlp P, Q;
-    if (int rc = mlp_of(e, actor, "pmg_policy_grad_device (actor)", P)) return rc;
-    if (int rc = mlp_of(e, critic, "pmg_policy_grad_device (critic)", Q)) return rc;
+    if (int rc = mlp_of(e, actor, who_actor, P)) return rc;
+    if (int rc = mlp_of(e, critic, who_critic, Q)) return rc;
     const int Dx = P.width[0], A = P.width[P.L];
     if (int rc = critic_of(e, Q, Dx + A, who)) return rc;
     if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
@@ -1514,8 +1515,18 @@ int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* crit
     if (g->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)g->batch);
     if (!g->d_x) return fail(e, PMG_E_INVALID, "%s: d_x is null", who);
     if (!std::isfinite(g->gscale) || !std::isfinite(g->l2scale)) return fail(e, PMG_E_INVALID, "%s: gscale %g or l2scale %g is not finite", who, (double)g->gscale, (double)g->l2scale);
-    if (!g->grads && !g->d_action && !g->d_out && !g->d_q && !g->d_gaction)
-        return fail(e, PMG_E_INVALID, "%s: grads, d_action, d_out, d_q and d_gaction are all null: nothing to do", who);
+    if (with_bc) {
+        if (!bc) return fail(e, PMG_E_INVALID, "%s: bc is null", who);
+        if (bc->struct_size != (int32_t)sizeof(pmg_policy_bc)) return fail(e, PMG_E_INVALID, "%s: bc.struct_size %d != %zu", who, bc->struct_size, sizeof(pmg_policy_bc));
+        if (!std::isfinite(bc->bcscale)) return fail(e, PMG_E_INVALID, "%s: bcscale %g is not finite", who, (double)bc->bcscale);
+        if (bc->q_filter != 0 && bc->q_filter != 1) return fail(e, PMG_E_INVALID, "%s: q_filter %d must be 0 or 1", who, bc->q_filter);
+        if (bc->demo_begin < 0 || bc->demo_begin > g->batch) return fail(e, PMG_E_INVALID, "%s: demo_begin %lld is outside [0, %lld]", who, (long long)bc->demo_begin, (long long)g->batch);
+        if (!bc->d_demo_action && bc->demo_begin < g->batch) return fail(e, PMG_E_INVALID, "%s: d_demo_action is null with demonstration rows from %lld", who, (long long)bc->demo_begin);
+        if ((((size_t)bc->d_demo_action | (size_t)bc->d_q_demo) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: d_demo_action or d_q_demo is not aligned to 4 bytes", who);
+        if (bc->d_demo_action && bc->demo_action_stride < A) return fail(e, PMG_E_INVALID, "%s: demo_action_stride %lld < %d", who, (long long)bc->demo_action_stride, A);
+    }
+    if (!g->grads && !g->d_action && !g->d_out && !g->d_q && !g->d_gaction && !(with_bc && (bc->d_q_demo || bc->d_filter)))
+        return fail(e, PMG_E_INVALID, "%s: grads and every output are null: nothing to do", who);
     if (g->grads) if (int rc = params_of(e, P, g->grads, false, who, "grads")) return rc;
     if ((((size_t)g->d_x | (size_t)g->d_action | (size_t)g->d_out | (size_t)g->d_q | (size_t)g->d_gaction | (size_t)g->d_work) & 3) != 0)
         return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
@@ -1543,8 +1554,14 @@ int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* crit
     PmgPolicy X;
     X.gscale = g->gscale; X.l2scale = g->l2scale;
     X.action = g->d_action; X.as = g->action_stride; X.q = g->d_q; X.ga = g->d_gaction; X.gas = g->gaction_stride;
+    PmgPolicyBc D;
+    memset(&D, 0, sizeof(D));
+    if (with_bc) {
+        D.begin = bc->demo_begin; D.ad = bc->d_demo_action; D.ads = bc->demo_action_stride; D.bcscale = bc->bcscale; D.q_filter = bc->q_filter;
+        D.qd = bc->d_q_demo; D.filter = bc->d_filter;
+    }
     if (!chunked) {
-        HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, nullptr, nullptr, e->stream));
+        HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, nullptr, nullptr, e->stream, with_bc ? &D : nullptr));
         return PMG_OK;
     }
     PmgSegs T;
@@ -1557,8 +1574,19 @@ int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* crit
         n++;
         if (P.b[l]) { K.pb[l] = K.part + T.end[n - 1]; n++; }
     }
-    HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, &K, &T, e->stream));
+    HIP_TRY(e, pmg_launch_policy_grad(P, Q, G, X, &K, &T, e->stream, with_bc ? &D : nullptr));
     return PMG_OK;
+}
+int pmg_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, int64_t chunk_rows)
+{
+    return policy_grad_call(e, "pmg_policy_grad_device", "pmg_policy_grad_device (actor)", "pmg_policy_grad_device (critic)", actor, critic, g, false, nullptr,
+                            chunk_rows);
+}
+/* ---- the same with the behaviour-cloning term and its Q-filter ---- */
+int pmg_policy_grad_bc_device(pmg_env* e, const pmg_mlp* actor, const pmg_mlp* critic, const pmg_policy_grad* g, const pmg_policy_bc* bc, int64_t chunk_rows)
+{
+    return policy_grad_call(e, "pmg_policy_grad_bc_device", "pmg_policy_grad_bc_device (actor)", "pmg_policy_grad_bc_device (critic)", actor, critic, g, true, bc,
+                            chunk_rows);
 }
 
 /* ---- SAC's actor half in one call and the temperature step ---- */

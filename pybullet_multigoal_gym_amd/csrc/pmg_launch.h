@@ -176,8 +176,19 @@ struct PmgPolicy {
     float* q;
     float* ga; long long gas;
 };
+/* the behaviour-cloning term of pmg_policy_grad_bc_device, validated by the caller: rows b >= begin are demonstrations with
+ * the action ad[b] (ad [B, A] at ads, indexed by the batch row; null only when begin == B); qd [B] (written from begin on) and filter [B]
+ * bytes (every row) may be null.  D == null launches pmg_policy_grad_device's kernel, and so does begin == B, with the filter zeroed behind it. */
+struct PmgPolicyBc {
+    long long begin;
+    const float* ad; long long ads;
+    float bcscale;
+    int q_filter;
+    float* qd;
+    unsigned char* filter;
+};
 hipError_t pmg_launch_policy_grad(const PmgMlp& actor, const PmgMlp& critic, const PmgGrad& G, const PmgPolicy& X, const PmgGradChunks* Q,
-                                  const PmgSegs* T, hipStream_t s);
+                                  const PmgSegs* T, hipStream_t s, const PmgPolicyBc* D = nullptr);
 /* SAC's actor half in one call (pmg_sac_policy_grad_device), validated by the caller.  actor.B = critic.B rows of G.x
  * [B, actor.width[0]]; G carries the ACTOR's arguments as for pmg_launch_policy_grad (grads, dw / db, wh / wd; everything else null).  H: the
  * head's arguments, H.action / H.as = where a [B, A] is written and read back in front of every critic (the caller's d_action at its stride,

@@ -1613,11 +1613,125 @@ __global__ void __launch_bounds__(256, 2) pmg_k_policy_grad_rows(PmgMlp P, PmgMl
         __syncthreads();                                         /* the next tile's rows overwrite this one's */
     }
 }
+/* The same with a behaviour-cloning term on the demonstration rows and its Q-filter (pmg_policy_grad_bc_device, DESIGN.md 3.18):
+ * pmg_k_policy_grad_rows, pass for pass, plus what is marked `bc` below.  A tile that holds a demonstration row (a workgroup-uniform
+ * branch) FIRST runs the critic on x | ad -- pmg_k_mlp<MlpCatRows>'s gather and layers, the chain of pmg_q_device --; qd then waits in a
+ * register of the row's thread (t < 32), as q1 does in pmg_k_td3_target, while the tile goes through the passes of the sibling unchanged.
+ * Stale tile: the pass leaves the critic's activations (which may be inf) on the tile exactly as the previous tile of the grid loop leaves
+ * its own, and the actor's gather behind it writes every column the actor's layer 0 reads -- [0, Dx) and the padding column of an odd Dx,
+ * all 32 rows, rows past the batch as zeros -- as it does there; the pass's own gather writes columns [0, Dx + A) and the padding column of
+ * an odd Dx + A the same way.  Once q exists the row's thread forms the filter flag into flt[]; the barrier behind the critic's head
+ * fences it from the hand-back, whose thread (row, j) reads its row's flag and ad[row][j] from the caller's table.  The next tile's flags
+ * are written behind the barriers of its own forward passes, so no reader of this tile's is still under way. */
+/* the rows x[r] | ad[r] of the demonstration pass: MlpCatRows, except that a row below `begin` takes the action of row `begin` -- no
+ * demonstration action below demo_begin is read; what the chain makes of such a row is used by nobody */
+struct MlpDemoRows {
+    const float* __restrict__ x; long long xs; const float* __restrict__ a; long long as; int Dx; long long begin;
+    __device__ __forceinline__ float at(long long r, int col) const { return col < Dx ? x[r * xs + col] : a[(r < begin ? begin : r) * as + (col - Dx)]; }
+};
+/* P, Q, G, X: as for pmg_k_policy_grad_rows; D: the demonstrations and the filter */
+__global__ void __launch_bounds__(256, 2) pmg_k_policy_grad_bc_rows(PmgMlp P, PmgMlp Q, PmgGrad G, PmgPolicy X, PmgPolicyBc D)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    __shared__ unsigned char flt[MLP_ROWS];                      /* bc: f of the tile's rows */
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L];
+    const MlpRawRows S = {G.x, G.xs};
+    float* __restrict__ stash = G.grads ? G.wd[P.L - 1] : nullptr;
+    const bool back = G.grads || X.ga, critic = back || X.q || D.filter;
+    const int r = t >> 3;                                        /* the row of this thread in both hand-overs: 8 units of all 32 rows per pass */
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS, row = row0 + r;
+        float qd = 0.f;
+        if (row0 + MLP_ROWS > D.begin) {                         /* bc: the demonstration pass, step 2b (the launcher sees to begin < B) */
+            const MlpDemoRows SD = {G.x, G.xs, D.ad, D.ads, Dx, D.begin};
+            mlp_gather(tile, SD, row0, P.B, Dx + A, (Dx + A + 1) & ~1, t);
+            __syncthreads();
+            mlp_layers(tile, Q, lane, wave, col);
+            if (t < MLP_ROWS && row0 + t < P.B && row0 + t >= D.begin) {
+                const float z = tile[t * MLP_LD];
+                qd = Q.out_act ? tanhf(z) : z;
+                if (D.qd) D.qd[row0 + t] = qd;
+            }
+            __syncthreads();                                     /* qd is read: column 0 is free */
+        }
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        unsigned int am1 = 0, am2 = 0, am3 = 0, cm1 = 0, cm2 = 0, cm3 = 0;
+        mlp_layers_saved(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+        for (int lo = (A - 1) & ~7; lo >= 0; lo -= 8) {          /* the hand-over */
+            const int j = lo + (t & 7);
+            const float z = j < A ? tile[r * MLP_LD + j] : 0.f;
+            __syncthreads();                                     /* the pass has read its z: columns [Dx + lo, Dx + lo + 8) are free */
+            if (j < A) {
+                const float o = P.out_act ? tanhf(z) : z, a = fminf(fmaxf(o, -1.f), 1.f);
+                tile[r * MLP_LD + Dx + j] = row < P.B ? a : 0.f;
+                if (row < P.B) {
+                    if (X.action) X.action[row * X.as + j] = a;
+                    if (G.out) G.out[row * G.os + j] = o;
+                    if (stash) stash[row * A + j] = o;
+                }
+            }
+        }
+        if (critic) {
+            mlp_gather(tile, S, row0, P.B, Dx, Dx, t);           /* columns below Dx: no pass wrote them, every pass is done reading */
+            if ((Dx + A) & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + Dx + A] = 0.f; }
+            __syncthreads();
+            mlp_layers_masked(tile, Q, lane, wave, col, cm1, cm2, cm3);
+            if (t < MLP_ROWS) {
+                float d = 0.f;
+                if (row0 + t < P.B) {
+                    const float z = tile[t * MLP_LD], q = Q.out_act ? tanhf(z) : z;
+                    if (X.q) X.q[row0 + t] = q;
+                    d = Q.out_act ? X.gscale * fmaf(-q, q, 1.f) : X.gscale;
+                    const unsigned char f = row0 + t >= D.begin && (!D.q_filter || qd > q);   /* bc: step 2c */
+                    flt[t] = f;
+                    if (D.filter) D.filter[row0 + t] = f;
+                }
+                tile[t * MLP_LD] = d;
+            }
+            __syncthreads();
+        }
+        if (back) mlp_backward_action(tile, Q, Dx, X.ga, X.gas, row0, lane, wave, col, cm1, cm2, cm3);
+        if (G.grads) {
+            for (int lo = 0; lo < A; lo += 8) {                  /* the hand-back */
+                const int j = lo + (t & 7);
+                const float ga = j < A ? tile[r * MLP_LD + Dx + j] : 0.f;
+                __syncthreads();                                 /* the pass has read its ga: columns [lo, lo + 8) are free */
+                if (j < A) {
+                    float d = 0.f;
+                    if (row < P.B) {
+                        const float o = stash[row * A + j];
+                        float g = fmaf(X.l2scale, o, (o >= -1.f && o <= 1.f) ? ga : 0.f);
+                        if (flt[r]) {                            /* bc: step 4, the difference rounded once */
+                            const float e = o - D.ad[row * D.ads + j];
+                            g = fmaf(D.bcscale, e, g);
+                        }
+                        d = P.out_act ? g * fmaf(-o, o, 1.f) : g;
+                        stash[row * A + j] = d;
+                    }
+                    tile[r * MLP_LD + j] = d;
+                }
+            }
+            if (A & 1) { if (t < MLP_ROWS) tile[t * MLP_LD + A] = 0.f; }
+            __syncthreads();
+            mlp_backward(tile, P, G, row0, lane, wave, col, am1, am2, am3);
+        }
+        __syncthreads();                                         /* the next tile's rows overwrite this one's */
+    }
+}
 hipError_t pmg_launch_policy_grad(const PmgMlp& P, const PmgMlp& Q, const PmgGrad& G, const PmgPolicy& X, const PmgGradChunks* C, const PmgSegs* T,
-                                  hipStream_t s)
+                                  hipStream_t s, const PmgPolicyBc* D)
 {
     if (P.B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pmg_k_policy_grad_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, Q, G, X);
+    /* a batch without a demonstration row (begin == B) is the sibling's: its kernel, which holds 45 fewer spilled SGPRs (DESIGN.md 3.18), and
+     * a filter of zeros */
+    if (D && D->begin < P.B) hipLaunchKernelGGL(pmg_k_policy_grad_bc_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, Q, G, X, *D);
+    else {
+        hipLaunchKernelGGL(pmg_k_policy_grad_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, Q, G, X);
+        if (D && D->filter) if (hipError_t err = hipMemsetAsync(D->filter, 0, (size_t)P.B, s)) return err;
+    }
     if (G.grads) {
         const MlpRawRows S = {G.x, G.xs};
         if (!C) hipLaunchKernelGGL((pmg_k_mlp_grad_weights<MlpRawRows>), dim3(pmg_grad_w_tiles(P)), dim3(64), 0, s, S, P, G);
