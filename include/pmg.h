@@ -711,6 +711,133 @@ typedef struct pmg_sac_alpha {
 } pmg_sac_alpha;
 int pmg_sac_alpha_device(pmg_env* env, const pmg_sac_alpha* a);
 
+/* ---- PPO on whole rollouts (normative), float32 unless said otherwise ----
+ * Four calls beside the existing ones: generalised advantage estimation, the advantage normaliser, the clipped-surrogate gradient of a Gaussian
+ * actor and the statistics of a minibatch.  Each is stream-ordered on the handle's stream, syncs nothing, writes only its outputs (and d_work)
+ * and touches no state of the handle; each is bit-reproducible and independent of the grid and of the number of CUs.
+ *
+ * pmg_gae_device: T steps of N envs.  Every table is addressed by (t, i) at ptr + t * time_stride + i * env_stride (floats; either stride may
+ * be negative, an input's may be 0), so a time-major [T, N] table (strides N, 1), an env-major [N, T] one (1, T) and a column of recorded
+ * packed rows read in place (strides N * packed_dim, packed_dim) are the same call.  One chain per env, t = T-1 ... 0:
+ *     gl = gamma * lambda                                  (one float multiply, on the host)
+ *     nv = terminal[t, i] != 0 ? +0.0f : value_next[t, i];   delta = fmaf(gamma, nv, reward[t, i]) - value[t, i]
+ *     adv[t, i] = (t == T-1 || cut[t, i] != 0) ? delta : fmaf(gl, adv[t+1, i], delta);    ret[t, i] = adv[t, i] + value[t, i]
+ * d_value_next[t, i] is V of the state that step t led to BEFORE any reset: with a [T+1, N] value table of states that were never reset it is
+ * d_value + time_stride; after pmg_reset_done_device the row t+1 of such a table holds the NEW episode's first state, and the caller passes
+ * the values of the recorded successor rows as a table of its own.  All episodes of this library end by TimeLimit, so the packed row's `done`
+ * column is a truncation: it is d_cut (the chain restarts, the bootstrap stays), never d_terminal.  d_terminal (no bootstrap) may be the
+ * goal_achieved column if the learner wants that.  d_cut NULL: no boundary but the last step; d_terminal NULL: every step bootstraps.  An
+ * env's results depend on its own column only.  The outputs overlap no input and not each other (not checked).
+ * PMG_E_INVALID, nothing launched: gamma or lambda outside [0, 1] or NaN; steps < 0 or envs < 0; steps * envs >= 2^31; d_reward, d_value,
+ * d_value_next or d_adv NULL; a pointer off 4 bytes; an output (d_adv, d_ret) whose strides could make two (t, i) alias: with a = |time_stride|,
+ * b = |env_stride| the call requires a >= 1 when steps > 1, b >= 1 when envs > 1, and a >= envs * b or b >= steps * a (sufficient, not
+ * necessary: a table with gaps in both directions is refused); a wrong struct_size.  steps == 0 or envs == 0 is a successful no-op. */
+typedef struct pmg_gae {
+    int32_t struct_size, reserved;
+    float gamma, lambda;                 /* each in [0, 1] */
+    int64_t steps, envs;                 /* T, N */
+    const float* d_reward; int64_t reward_time_stride, reward_env_stride;
+    const float* d_value; int64_t value_time_stride, value_env_stride;                      /* V(s_t) */
+    const float* d_value_next; int64_t value_next_time_stride, value_next_env_stride;       /* V of the state step t led to, before any reset */
+    const float* d_cut; int64_t cut_time_stride, cut_env_stride;                            /* or NULL; != 0: an episode ends behind step t */
+    const float* d_terminal; int64_t terminal_time_stride, terminal_env_stride;             /* or NULL; != 0: no bootstrap */
+    float* d_adv; int64_t adv_time_stride, adv_env_stride;                                  /* required */
+    float* d_ret; int64_t ret_time_stride, ret_env_stride;                                  /* or NULL: adv + value */
+} pmg_gae;
+int pmg_gae_device(pmg_env* env, const pmg_gae* g);
+
+/* pmg_adv_stats_device / pmg_adv_apply_device: the advantage normaliser over M = count contiguous floats, one workgroup of 256 threads for the
+ * statistics.  Thread k accumulates in DOUBLE s = s + x, q = fma(x, x, q) over the elements b = k (mod 256) in ascending order from +0.0;
+ * thread 0 adds the 256 partial sums in ascending order from +0.0 (S, Q), then
+ *     mean = S / M;   var = max((Q - S * mean) / (M - ddof), 0);   d_stats[0] = (float)mean;   d_stats[1] = (float)(1 / (sqrt(var) + (double)eps))
+ * mean is bit-defined (x * x is exact in double, so the fma is one rounding either way); d_stats[1] goes through the build's double sqrt and
+ * division (and S * mean may be fused into the subtraction) and is held to a float64 model.  eps == 0 with var == 0 gives +inf.
+ * apply: y[b] = (x[b] - d_stats[0]) * d_stats[1], two roundings; d_y == d_x is allowed; the statistics are read from device memory on the
+ * stream, so nothing waits between the two calls.
+ * PMG_E_INVALID, nothing launched: count < 0; ddof not 0 or 1; count >= 1 and count - ddof < 1; eps negative or not finite; a NULL pointer or
+ * one off 4 bytes; a wrong struct_size.  count == 0 is a successful no-op that writes nothing. */
+typedef struct pmg_adv_stats {
+    int32_t struct_size, ddof;           /* ddof: 0 (population) or 1 (sample) */
+    float eps;                           /* finite, >= 0 */
+    int32_t reserved;
+    int64_t count;                       /* M */
+    const float* d_x;                    /* [M] */
+    float* d_stats;                      /* [2]: mean, 1 / (std + eps) */
+} pmg_adv_stats;
+int pmg_adv_stats_device(pmg_env* env, const pmg_adv_stats* s);
+int pmg_adv_apply_device(pmg_env* env, const float* d_x, int64_t count, const float* d_stats, float* d_y);
+
+/* pmg_ppo_policy_grad_device: the gradient of PPO's clipped surrogate and entropy bonus
+ *     pscale * sum_b min(rho_b adv_b, clamp(rho_b, clip_lo, clip_hi) adv_b) + escale * sum_b sum_j ls_bj
+ * with respect to the parameters of a Gaussian actor (above: width[L] == 2 A, out_activation == 0, A <= 128) in one call; PPO's loss
+ * -mean(min(...)) - ent_coef * mean(entropy) is pscale = -1 / B, escale = -ent_coef / B.  rho is the ratio of the new policy to the one that drew
+ * the action, both evaluated at the recorded pre-squash sample u; the tanh correction and log 2 pi are the same on both sides and are left
+ * out.  The entropy is that of the PRE-SQUASH Gaussian, sum_j ls_j + const: a squashed policy's entropy has no closed form, and the usual
+ * estimate -log pi(a) would need a fresh sample; the bonus therefore acts on the log-stds inside the clamp and on nothing else.
+ * Per row b (x[b]; zo[b] [2 A] and n[b] [A]: the d_preact and d_noise that pmg_sac_act_env_device / pmg_sac_sample_device returned when the
+ * action was drawn; adv[b]), per unit j < A:
+ *   1. z = the actor's layer chain on x[b] (bit-defined, unchanged);  m = z[j];  ls = fminf(fmaxf(z[A + j], ls_lo), ls_hi);
+ *      inr = z[A + j] >= ls_lo && z[A + j] <= ls_hi.
+ *   2. lso = fminf(fmaxf(zo[A + j], ls_lo), ls_hi);  u = fmaf(expf(lso), n[j], zo[j]) -- the very u of the head above, the env received tanhf(u);
+ *      lo_j = fmaf(-0.5f * n[j], n[j], -lso).
+ *   3. isd = expf(-ls);  w = (u - m) * isd;  ln_j = fmaf(-0.5f * w, w, -ls).
+ *   4. lr: acc = +0.0f; acc = acc + (ln_j - lo_j) for j ascending, ONE chain;  rho = expf(lr).
+ *   5. clipped = (adv > 0 && rho > clip_hi) || (adv < 0 && rho < clip_lo);  k = clipped ? +0.0f : (pscale * adv) * rho.  That is the surrogate's
+ *      gradient everywhere but on ties, where both branches of the min carry the same gradient.  A NaN adv or rho is not clipped.
+ *   6. g_mu[j] = k * (w * isd);  g_ls[j] = inr ? fmaf(k, fmaf(w, w, -1.f), escale) : +0.0f  (the clamp's derivative as in pmg_sac_policy_grad).
+ *   7. delta_{L-1} = g_mu | g_ls, and from there dW_l and db_l of the actor exactly as pmg_mlp_grad_device (chunk_rows == 0) or
+ *      pmg_mlp_grad_chunked_device (chunk_rows >= 2, even) forms them from d_gout = g.
+ * d_ratio [B] (rho), d_logratio [B] (lr), d_clipped [B] bytes (0 / 1) and d_ghead [B, 2 A] (g_mu | g_ls) may each be NULL.  grads == NULL:
+ * these alone are produced (steps 6 and 7 run only for d_ghead) and d_work is not touched and may be NULL.  z is bit-defined; lr, rho and g
+ * go through the build's expf and are held to a float32 model.  A row's outputs do not depend on the batch it is in; dW and db depend on the
+ * row order and on chunk_rows and on nothing else; two calls on the same inputs give the same bits.
+ * Workspace: pmg_ppo_policy_grad_work_floats = the actor's pmg_mlp_grad_work_floats (chunk_rows == 0) or pmg_mlp_grad_chunked_work_floats
+ * figure, laid out as those calls lay it out; < 0 for an invalid actor, batch or chunk_rows.  Between steps 3 and 6, w and isd of a (row, unit)
+ * are kept where its delta_{L-1} will be (without grads: in d_ghead).
+ * PMG_E_INVALID, nothing launched and nothing written: everything pmg_sac_sample_device rejects in the actor, ls_lo and ls_hi; pscale or escale
+ * not finite; clip_lo or clip_hi NaN, clip_lo < 0 or clip_lo > clip_hi (clip_hi may be +inf); batch < 0; d_x, d_preact_old, d_noise or d_adv NULL;
+ * grads and every output NULL; everything pmg_policy_grad_device rejects in grads, chunk_rows, d_work and work_floats (with grads); a float
+ * pointer off 4 bytes; a stride below its width; a wrong struct_size.  batch == 0 is a successful no-op that leaves grads untouched. */
+typedef struct pmg_ppo_policy_grad {
+    int32_t struct_size, reserved;
+    float pscale;                        /* finite; -1 / B for -mean of the clipped surrogate */
+    float escale;                        /* finite; -ent_coef / B; 0: no entropy bonus */
+    float clip_lo, clip_hi;              /* 1 - eps, 1 + eps as floats; 0 <= clip_lo <= clip_hi */
+    float ls_lo, ls_hi;                  /* as pmg_sac_sample: the clamp the action was drawn with */
+    int64_t batch;
+    const float* d_x; int64_t x_stride;                      /* [B, Dx] */
+    const float* d_preact_old; int64_t preact_old_stride;    /* [B, 2 A]: zo */
+    const float* d_noise; int64_t noise_stride;              /* [B, A]:   n */
+    const float* d_adv;                                      /* [B] */
+    const pmg_mlp_params* grads;         /* the actor's dW / db, overwritten; NULL: the outputs below only */
+    float* d_ratio;                      /* [B] or NULL: rho */
+    float* d_logratio;                   /* [B] or NULL: lr */
+    uint8_t* d_clipped;                  /* [B] or NULL: 1 where the clip cut the gradient */
+    float* d_ghead; int64_t ghead_stride;                    /* [B, 2 A] or NULL: g_mu | g_ls */
+    float* d_work; int64_t work_floats;  /* scratch with grads, at least pmg_ppo_policy_grad_work_floats(actor, batch, chunk_rows) */
+} pmg_ppo_policy_grad;
+int64_t pmg_ppo_policy_grad_work_floats(const pmg_mlp* actor, int64_t batch, int64_t chunk_rows);
+int pmg_ppo_policy_grad_device(pmg_env* env, const pmg_mlp* actor, const pmg_ppo_policy_grad* g, int64_t chunk_rows);
+
+/* pmg_ppo_stats_device: what a PPO learner logs and stops early on, from the per-row outputs above and the advantages of a minibatch; one
+ * workgroup, the two-level chain of pmg_sac_alpha_device for each of four float32 sums (thread t over the rows b = t (mod 256) ascending from
+ * +0.0, thread 0 over the 256 partial sums ascending from +0.0):
+ *     d_stats[0] = mean of (rho - 1.f) - lr                                     the approximate KL divergence old || new
+ *     d_stats[1] = mean of (clipped != 0 ? 1.f : 0.f)                           the clip fraction
+ *     d_stats[2] = mean of fminf(rho * adv, fminf(fmaxf(rho, clip_lo), clip_hi) * adv)    the clipped surrogate
+ *     d_stats[3] = mean of lr
+ * each quotient total / (float)batch correctly rounded.  Bit-defined.
+ * PMG_E_INVALID, nothing launched: batch <= 0; a NULL pointer; a float pointer off 4 bytes; clip_lo or clip_hi as refused above; a wrong
+ * struct_size. */
+typedef struct pmg_ppo_stats {
+    int32_t struct_size, reserved;
+    float clip_lo, clip_hi;
+    int64_t batch;
+    const float* d_ratio; const float* d_logratio; const uint8_t* d_clipped; const float* d_adv;   /* [B] each */
+    float* d_stats;                      /* [4]: approximate KL, clip fraction, surrogate, mean log-ratio */
+} pmg_ppo_stats;
+int pmg_ppo_stats_device(pmg_env* env, const pmg_ppo_stats* s);
+
 /* Checkpoint / test hooks (no reference equivalent).
  * state: [N, state_dim] float32, layout documented in DESIGN.md (with use_curriculum the row ends with 16
  * floats of curriculum state: prob[5] generated[5] goal_step; chest tasks prob[6] generated[6] goal_step). */

@@ -127,6 +127,30 @@ class PmgSacAlpha(C.Structure):
                 ('eps', C.c_float), ('reserved2', C.c_int32), ('step', C.c_int64), ('batch', C.c_int64), ('d_logp', C.c_void_p), ('d_state', C.c_void_p)]
 
 
+class PmgGae(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('gamma', C.c_float), ('lam', C.c_float), ('steps', C.c_int64), ('envs', C.c_int64)] + \
+               [f for name in ('reward', 'value', 'value_next', 'cut', 'terminal', 'adv', 'ret')
+                for f in (('d_' + name, C.c_void_p), (name + '_time_stride', C.c_int64), (name + '_env_stride', C.c_int64))]
+
+
+class PmgAdvStats(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('ddof', C.c_int32), ('eps', C.c_float), ('reserved', C.c_int32), ('count', C.c_int64), ('d_x', C.c_void_p),
+                ('d_stats', C.c_void_p)]
+
+
+class PmgPpoPolicyGrad(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('pscale', C.c_float), ('escale', C.c_float), ('clip_lo', C.c_float), ('clip_hi', C.c_float),
+                ('ls_lo', C.c_float), ('ls_hi', C.c_float), ('batch', C.c_int64), ('d_x', C.c_void_p), ('x_stride', C.c_int64), ('d_preact_old', C.c_void_p),
+                ('preact_old_stride', C.c_int64), ('d_noise', C.c_void_p), ('noise_stride', C.c_int64), ('d_adv', C.c_void_p), ('grads', C.POINTER(PmgMlpParams)),
+                ('d_ratio', C.c_void_p), ('d_logratio', C.c_void_p), ('d_clipped', C.c_void_p), ('d_ghead', C.c_void_p), ('ghead_stride', C.c_int64),
+                ('d_work', C.c_void_p), ('work_floats', C.c_int64)]
+
+
+class PmgPpoStats(C.Structure):
+    _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('clip_lo', C.c_float), ('clip_hi', C.c_float), ('batch', C.c_int64), ('d_ratio', C.c_void_p),
+                ('d_logratio', C.c_void_p), ('d_clipped', C.c_void_p), ('d_adv', C.c_void_p), ('d_stats', C.c_void_p)]
+
+
 class PmgAdam(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('reserved', C.c_int32), ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
                 ('step', C.c_int64)]
@@ -158,6 +182,8 @@ class PmgLibrary:
                'pmg_td3_target_work_floats', 'pmg_td3_target_device',
                'pmg_sac_sample_device', 'pmg_sac_act_env_device', 'pmg_sac_target_work_floats', 'pmg_sac_target_device',
                'pmg_sac_policy_grad_work_floats', 'pmg_sac_policy_grad_device', 'pmg_sac_alpha_device',
+               'pmg_gae_device', 'pmg_adv_stats_device', 'pmg_adv_apply_device', 'pmg_ppo_policy_grad_work_floats', 'pmg_ppo_policy_grad_device',
+               'pmg_ppo_stats_device',
                'pmg_comm_info', 'pmg_allgather_device', 'pmg_mlp_param_floats', 'pmg_mlp_params_pack_device', 'pmg_mlp_params_merge_device',
                'pmg_mlp_adam_merge_device', 'pmg_mlp_allreduce_work_floats', 'pmg_mlp_grad_allreduce_device', 'pmg_mlp_adam_allreduce_device',
                'pmg_norm_update_ranks_device', 'pmg_norm_update_env_ranks_device']
@@ -187,6 +213,7 @@ class PmgLibrary:
         L.pmg_td3_target_work_floats.restype = C.c_int64
         L.pmg_sac_target_work_floats.restype = C.c_int64
         L.pmg_sac_policy_grad_work_floats.restype = C.c_int64
+        L.pmg_ppo_policy_grad_work_floats.restype = C.c_int64
         L.pmg_mlp_param_floats.restype = C.c_int64
         L.pmg_mlp_allreduce_work_floats.restype = C.c_int64
 
@@ -519,6 +546,62 @@ class PmgHandle:
     def sac_alpha_device(self, a):
         """one Adam step on the log-temperature of a sac_alpha_struct(), then alpha = exp(log_alpha); stream-ordered, no host sync."""
         self._check(self.L.lib.pmg_sac_alpha_device(self.h, C.byref(a)))
+
+    # -- PPO on whole rollouts: GAE, the advantage normaliser, the clipped-surrogate gradient, the statistics (include/pmg.h, DESIGN.md 3.19) --
+    @staticmethod
+    def gae_struct(steps, envs, gamma, lam, reward, value, value_next, adv, cut=None, terminal=None, ret=None):
+        """pmg_gae; every table is (device pointer, time_stride, env_stride) in floats, or None where the call allows it."""
+        g = PmgGae()
+        g.struct_size, g.gamma, g.lam, g.steps, g.envs = C.sizeof(PmgGae), gamma, lam, steps, envs
+        for name, tab in (('reward', reward), ('value', value), ('value_next', value_next), ('cut', cut), ('terminal', terminal), ('adv', adv), ('ret', ret)):
+            if tab is not None:
+                setattr(g, 'd_' + name, tab[0])
+                setattr(g, name + '_time_stride', tab[1])
+                setattr(g, name + '_env_stride', tab[2])
+        return g
+
+    def gae_device(self, g):
+        """advantages (and returns) of a gae_struct(): one reverse chain per env; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_gae_device(self.h, C.byref(g)))
+
+    @staticmethod
+    def adv_stats_struct(count, d_x, d_stats, eps=1e-8, ddof=0):
+        """pmg_adv_stats from device pointers; d_stats: two floats, mean | 1 / (std + eps)."""
+        return PmgAdvStats(C.sizeof(PmgAdvStats), int(ddof), eps, 0, count, d_x, d_stats)
+
+    def adv_stats_device(self, s):
+        """mean and 1 / (std + eps) of the floats of an adv_stats_struct() into device memory; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_adv_stats_device(self.h, C.byref(s)))
+
+    def adv_apply_device(self, d_x_ptr, count, d_stats_ptr, d_y_ptr):
+        """y = (x - stats[0]) * stats[1] with the statistics read on the stream; d_y may be d_x; no host sync."""
+        self._check(self.L.lib.pmg_adv_apply_device(self.h, C.c_void_p(d_x_ptr), C.c_int64(count), C.c_void_p(d_stats_ptr), C.c_void_p(d_y_ptr)))
+
+    @staticmethod
+    def ppo_policy_grad_struct(batch, d_x, x_stride, d_preact_old, preact_old_stride, d_noise, noise_stride, d_adv, pscale, escale, clip_lo, clip_hi,
+                               ls_lo=-20.0, ls_hi=2.0, grads=None, d_ratio=None, d_logratio=None, d_clipped=None, d_ghead=None, ghead_stride=0, d_work=None,
+                               work_floats=0):
+        """pmg_ppo_policy_grad from device pointers (integers or None); grads: a params_struct() or None (it must outlive the call)."""
+        return PmgPpoPolicyGrad(C.sizeof(PmgPpoPolicyGrad), 0, pscale, escale, clip_lo, clip_hi, ls_lo, ls_hi, batch, d_x, x_stride, d_preact_old,
+                                preact_old_stride, d_noise, noise_stride, d_adv, C.pointer(grads) if grads is not None else None, d_ratio, d_logratio,
+                                d_clipped, d_ghead, ghead_stride, d_work, work_floats)
+
+    def ppo_policy_grad_work_floats(self, actor, batch, chunk_rows=0):
+        """floats of workspace pmg_ppo_policy_grad_device needs with grads: the actor's gradient figure (< 0: invalid)"""
+        return int(self.L.lib.pmg_ppo_policy_grad_work_floats(C.byref(actor), C.c_int64(batch), C.c_int64(chunk_rows)))
+
+    def ppo_policy_grad_device(self, actor, grad, chunk_rows=0):
+        """the Gaussian actor's gradient of PPO's clipped surrogate and entropy bonus of a ppo_policy_grad_struct(); stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_ppo_policy_grad_device(self.h, C.byref(actor), C.byref(grad), C.c_int64(chunk_rows)))
+
+    @staticmethod
+    def ppo_stats_struct(batch, d_ratio, d_logratio, d_clipped, d_adv, d_stats, clip_lo, clip_hi):
+        """pmg_ppo_stats from device pointers; d_stats: four floats, approximate KL | clip fraction | clipped surrogate | mean log-ratio."""
+        return PmgPpoStats(C.sizeof(PmgPpoStats), 0, clip_lo, clip_hi, batch, d_ratio, d_logratio, d_clipped, d_adv, d_stats)
+
+    def ppo_stats_device(self, s):
+        """the four means of a ppo_stats_struct() into device memory; stream-ordered, no host sync."""
+        self._check(self.L.lib.pmg_ppo_stats_device(self.h, C.byref(s)))
 
     # -- back-propagation, Adam, Polyak (include/pmg.h, DESIGN.md 3.11) --
     @staticmethod

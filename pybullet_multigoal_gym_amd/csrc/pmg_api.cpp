@@ -1710,6 +1710,189 @@ int pmg_sac_alpha_device(pmg_env* e, const pmg_sac_alpha* a)
     return PMG_OK;
 }
 
+/* ---- PPO on whole rollouts: GAE, the advantage normaliser, the clipped-surrogate gradient, the minibatch statistics ---- */
+/* an output table of pmg_gae_device holds T x N distinct elements by the rule of include/pmg.h: a = |ts| >= 1 when T > 1, b = |es| >= 1 when
+ * N > 1, and a >= N b or b >= T a.  T N < 2^31, so the products overflow only when the stride they are compared with is beyond 2^31 too */
+static bool gae_out_ok(int64_t T, int64_t N, int64_t ts, int64_t es)
+{
+    if (T <= 0 || N <= 0) return true;                             /* an empty table */
+    if (ts == INT64_MIN || es == INT64_MIN) return false;
+    const int64_t a = ts < 0 ? -ts : ts, b = es < 0 ? -es : es;
+    if ((T > 1 && a == 0) || (N > 1 && b == 0)) return false;
+    const bool time_major = b == 0 || a / b >= N, env_major = a == 0 || b / a >= T;   /* floor(a / b) >= N iff a >= N b */
+    return time_major || env_major;
+}
+int pmg_gae_device(pmg_env* e, const pmg_gae* g)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_gae_device";
+    if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
+    if (g->struct_size != (int32_t)sizeof(pmg_gae)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_gae));
+    if (!(g->gamma >= 0.f && g->gamma <= 1.f) || !(g->lambda >= 0.f && g->lambda <= 1.f))
+        return fail(e, PMG_E_INVALID, "%s: gamma %g and lambda %g must lie in [0, 1]", who, (double)g->gamma, (double)g->lambda);
+    if (g->steps < 0 || g->envs < 0) return fail(e, PMG_E_INVALID, "%s: steps %lld or envs %lld is negative", who, (long long)g->steps, (long long)g->envs);
+    if (g->steps > 0 && g->envs > 0 && (g->steps >= (1ll << 31) || g->envs >= (1ll << 31) || g->steps * g->envs >= (1ll << 31)))
+        return fail(e, PMG_E_INVALID, "%s: steps %lld x envs %lld is 2^31 or more", who, (long long)g->steps, (long long)g->envs);
+    if (!g->d_reward || !g->d_value || !g->d_value_next || !g->d_adv) return fail(e, PMG_E_INVALID, "%s: d_reward, d_value, d_value_next or d_adv is null", who);
+    if ((((size_t)g->d_reward | (size_t)g->d_value | (size_t)g->d_value_next | (size_t)g->d_cut | (size_t)g->d_terminal | (size_t)g->d_adv | (size_t)g->d_ret) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (!gae_out_ok(g->steps, g->envs, g->adv_time_stride, g->adv_env_stride) ||
+        (g->d_ret && !gae_out_ok(g->steps, g->envs, g->ret_time_stride, g->ret_env_stride)))
+        return fail(e, PMG_E_INVALID, "%s: the strides of d_adv (%lld, %lld) or d_ret (%lld, %lld) could put two (t, i) of %lld x %lld on one element", who,
+                    (long long)g->adv_time_stride, (long long)g->adv_env_stride, (long long)g->ret_time_stride, (long long)g->ret_env_stride, (long long)g->steps,
+                    (long long)g->envs);
+    if (g->steps == 0 || g->envs == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgGae X;
+    memset(&X, 0, sizeof(X));
+    X.T = g->steps; X.N = g->envs; X.gamma = g->gamma; X.gl = g->gamma * g->lambda;
+    X.reward = {g->d_reward, g->reward_time_stride, g->reward_env_stride};
+    X.value = {g->d_value, g->value_time_stride, g->value_env_stride};
+    X.value_next = {g->d_value_next, g->value_next_time_stride, g->value_next_env_stride};
+    X.cut = {g->d_cut, g->cut_time_stride, g->cut_env_stride};
+    X.term = {g->d_terminal, g->terminal_time_stride, g->terminal_env_stride};
+    X.adv = g->d_adv; X.ats = g->adv_time_stride; X.aes = g->adv_env_stride;
+    X.ret = g->d_ret; X.rts = g->ret_time_stride; X.res = g->ret_env_stride;
+    HIP_TRY(e, pmg_launch_gae(X, e->stream));
+    return PMG_OK;
+}
+
+int pmg_adv_stats_device(pmg_env* e, const pmg_adv_stats* s)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_adv_stats_device";
+    if (!s) return fail(e, PMG_E_INVALID, "%s: s is null", who);
+    if (s->struct_size != (int32_t)sizeof(pmg_adv_stats)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, s->struct_size, sizeof(pmg_adv_stats));
+    if (s->count < 0) return fail(e, PMG_E_INVALID, "%s: count %lld is negative", who, (long long)s->count);
+    if (s->ddof != 0 && s->ddof != 1) return fail(e, PMG_E_INVALID, "%s: ddof %d must be 0 or 1", who, s->ddof);
+    if (s->count >= 1 && s->count - s->ddof < 1) return fail(e, PMG_E_INVALID, "%s: count %lld - ddof %d is below 1", who, (long long)s->count, s->ddof);
+    if (!std::isfinite(s->eps) || !(s->eps >= 0.f)) return fail(e, PMG_E_INVALID, "%s: eps %g must be finite and >= 0", who, (double)s->eps);
+    if (!s->d_x || !s->d_stats) return fail(e, PMG_E_INVALID, "%s: d_x or d_stats is null", who);
+    if ((((size_t)s->d_x | (size_t)s->d_stats) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (s->count == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgAdvStats X;
+    X.x = s->d_x; X.M = s->count; X.ddof = s->ddof; X.eps = s->eps; X.stats = s->d_stats;
+    HIP_TRY(e, pmg_launch_adv_stats(X, e->stream));
+    return PMG_OK;
+}
+
+int pmg_adv_apply_device(pmg_env* e, const float* d_x, int64_t count, const float* d_stats, float* d_y)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_adv_apply_device";
+    if (count < 0) return fail(e, PMG_E_INVALID, "%s: count %lld is negative", who, (long long)count);
+    if (!d_x || !d_stats || !d_y) return fail(e, PMG_E_INVALID, "%s: d_x, d_stats or d_y is null", who);
+    if ((((size_t)d_x | (size_t)d_stats | (size_t)d_y) & 3) != 0) return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (count == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, pmg_launch_adv_apply(d_x, count, d_stats, d_y, e->stream));
+    return PMG_OK;
+}
+
+/* the clip of the surrogate; 0 or PMG_E_INVALID */
+static int ppo_clip_of(pmg_env* e, float lo, float hi, const char* who)
+{
+    if (std::isnan(lo) || std::isnan(hi) || lo < 0.f || lo > hi) return fail(e, PMG_E_INVALID, "%s: clip_lo %g / clip_hi %g must be ordered, clip_lo >= 0", who, (double)lo, (double)hi);
+    return PMG_OK;
+}
+/* the workspace is the actor's: pmg_mlp_grad_work_floats, or with chunk_rows the chunked figure */
+int64_t pmg_ppo_policy_grad_work_floats(const pmg_mlp* actor, int64_t batch, int64_t chunk_rows)
+{
+    const int64_t base = chunk_rows == 0 ? pmg_mlp_grad_work_floats(actor, batch) : pmg_mlp_grad_chunked_work_floats(actor, batch, chunk_rows);
+    if (base < 0) return -1;
+    const int A2 = actor->width[actor->num_layers];
+    if (A2 < 2 || (A2 & 1) != 0) return -1;
+    return base;
+}
+
+int pmg_ppo_policy_grad_device(pmg_env* e, const pmg_mlp* actor, const pmg_ppo_policy_grad* g, int64_t chunk_rows)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_ppo_policy_grad_device";
+    PmgMlp P;
+    if (int rc = mlp_of(e, actor, who, P)) return rc;
+    if (int rc = gaussian_of(e, P, who)) return rc;
+    const int Dx = P.width[0], A = P.width[P.L] / 2;
+    if (!g) return fail(e, PMG_E_INVALID, "%s: g is null", who);
+    if (g->struct_size != (int32_t)sizeof(pmg_ppo_policy_grad)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(pmg_ppo_policy_grad));
+    if (g->batch < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is negative", who, (long long)g->batch);
+    if (!g->d_x || !g->d_preact_old || !g->d_noise || !g->d_adv) return fail(e, PMG_E_INVALID, "%s: d_x, d_preact_old, d_noise or d_adv is null", who);
+    if (!std::isfinite(g->pscale) || !std::isfinite(g->escale)) return fail(e, PMG_E_INVALID, "%s: pscale %g or escale %g is not finite", who, (double)g->pscale, (double)g->escale);
+    if (int rc = ppo_clip_of(e, g->clip_lo, g->clip_hi, who)) return rc;
+    if (int rc = sac_clamp_of(e, g->ls_lo, g->ls_hi, who)) return rc;
+    if (!g->grads && !g->d_ratio && !g->d_logratio && !g->d_clipped && !g->d_ghead)
+        return fail(e, PMG_E_INVALID, "%s: grads, d_ratio, d_logratio, d_clipped and d_ghead are all null: nothing to do", who);
+    if (g->grads) if (int rc = params_of(e, P, g->grads, false, who, "grads")) return rc;
+    if ((((size_t)g->d_x | (size_t)g->d_preact_old | (size_t)g->d_noise | (size_t)g->d_adv | (size_t)g->d_ratio | (size_t)g->d_logratio | (size_t)g->d_ghead |
+          (size_t)g->d_work) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    if (g->x_stride < Dx || g->preact_old_stride < 2 * A || g->noise_stride < A || (g->d_ghead && g->ghead_stride < 2 * A))
+        return fail(e, PMG_E_INVALID, "%s: a stride is smaller than its width", who);
+    if (chunk_rows < 0 || chunk_rows == 1 || (chunk_rows & 1)) return fail(e, PMG_E_INVALID, "%s: chunk_rows %lld must be 0 (one chain) or even and >= 2", who, (long long)chunk_rows);
+    const int64_t C = chunk_rows ? g->batch / chunk_rows + (g->batch % chunk_rows != 0) : 1;
+    if (C > PMG_GRAD_MAX_CHUNKS)
+        return fail(e, PMG_E_INVALID, "%s: batch %lld in chunks of %lld rows is %lld chunks, more than %d", who, (long long)g->batch, (long long)chunk_rows, (long long)C, PMG_GRAD_MAX_CHUNKS);
+    const bool chunked = g->grads && C > 1;
+    const int64_t base = pmg_mlp_grad_work_floats(actor, g->batch);
+    const int64_t need = chunked ? pmg_mlp_grad_chunked_work_floats(actor, g->batch, chunk_rows) : base;
+    if (need < 0) return fail(e, PMG_E_INVALID, "%s: batch %lld is too large", who, (long long)g->batch);
+    if (g->grads && (!g->d_work || g->work_floats < need))
+        return fail(e, PMG_E_INVALID, "%s: d_work is null or work_floats %lld < %lld", who, (long long)g->work_floats, (long long)need);
+    if (g->batch == 0) return PMG_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    P.B = g->batch;
+    PmgGrad G;
+    memset(&G, 0, sizeof(G));
+    G.x = g->d_x; G.xs = g->x_stride; G.x_dim = Dx;
+    G.grads = g->grads ? 1 : 0;
+    for (int l = 0; l < P.L && g->grads; l++) { G.dw[l] = g->grads->d_weight[l]; G.db[l] = P.b[l] ? g->grads->d_bias[l] : nullptr; }
+    if (g->grads) pmg_grad_work_layout(P, P.B, g->d_work, &G);
+    PmgPpoPolicy X;
+    memset(&X, 0, sizeof(X));
+    X.pscale = g->pscale; X.escale = g->escale; X.clip_lo = g->clip_lo; X.clip_hi = g->clip_hi; X.ls_lo = g->ls_lo; X.ls_hi = g->ls_hi;
+    X.zo = g->d_preact_old; X.zos = g->preact_old_stride; X.n = g->d_noise; X.ns = g->noise_stride; X.adv = g->d_adv;
+    X.ratio = g->d_ratio; X.logratio = g->d_logratio; X.clipped = g->d_clipped;
+    X.ghead = g->d_ghead; X.ghs = g->ghead_stride;
+    if (g->grads) { X.stash = G.wd[P.L - 1]; X.ss = 2 * A; }
+    else if (g->d_ghead) { X.stash = g->d_ghead; X.ss = g->ghead_stride; }
+    if (!chunked) {
+        HIP_TRY(e, pmg_launch_ppo_policy_grad(P, G, X, nullptr, nullptr, e->stream));
+        return PMG_OK;
+    }
+    PmgSegs T;
+    segs_of(P, g->grads, g->grads->d_weight, g->grads->d_bias, nullptr, nullptr, T);
+    PmgGradChunks K;
+    memset(&K, 0, sizeof(K));
+    K.R = chunk_rows; K.C = C; K.P = grad_chunk_params(actor); K.tiles = pmg_grad_w_tiles(P); K.part = g->d_work + base;
+    for (int l = 0, n = 0; l < P.L; l++) {                          /* tensor n of T starts at T.end[n - 1] */
+        K.pw[l] = K.part + (n ? T.end[n - 1] : 0);
+        n++;
+        if (P.b[l]) { K.pb[l] = K.part + T.end[n - 1]; n++; }
+    }
+    HIP_TRY(e, pmg_launch_ppo_policy_grad(P, G, X, &K, &T, e->stream));
+    return PMG_OK;
+}
+
+int pmg_ppo_stats_device(pmg_env* e, const pmg_ppo_stats* s)
+{
+    if (!e) return PMG_E_INVALID;
+    const char* who = "pmg_ppo_stats_device";
+    if (!s) return fail(e, PMG_E_INVALID, "%s: s is null", who);
+    if (s->struct_size != (int32_t)sizeof(pmg_ppo_stats)) return fail(e, PMG_E_INVALID, "%s: struct_size %d != %zu", who, s->struct_size, sizeof(pmg_ppo_stats));
+    if (s->batch <= 0) return fail(e, PMG_E_INVALID, "%s: batch %lld must be >= 1", who, (long long)s->batch);
+    if (int rc = ppo_clip_of(e, s->clip_lo, s->clip_hi, who)) return rc;
+    if (!s->d_ratio || !s->d_logratio || !s->d_clipped || !s->d_adv || !s->d_stats) return fail(e, PMG_E_INVALID, "%s: a pointer is null", who);
+    if ((((size_t)s->d_ratio | (size_t)s->d_logratio | (size_t)s->d_adv | (size_t)s->d_stats) & 3) != 0)
+        return fail(e, PMG_E_INVALID, "%s: a float pointer is not aligned to 4 bytes", who);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PmgPpoStats X;
+    X.ratio = s->d_ratio; X.logratio = s->d_logratio; X.clipped = s->d_clipped; X.adv = s->d_adv; X.B = s->batch;
+    X.clip_lo = s->clip_lo; X.clip_hi = s->clip_hi; X.stats = s->d_stats;
+    HIP_TRY(e, pmg_launch_ppo_stats(X, e->stream));
+    return PMG_OK;
+}
+
 /* state row = hot(32) | cold(16) | goal(16) | blocks(13 nb)    */
 int pmg_get_state(pmg_env* e, float* state)
 {

@@ -216,6 +216,43 @@ struct PmgSacAlpha {
     float* state;
 };
 hipError_t pmg_launch_sac_alpha(const PmgSacAlpha& X, hipStream_t s);
+/* PPO on whole rollouts (pmg_gae_device, pmg_adv_stats_device, pmg_adv_apply_device, pmg_ppo_policy_grad_device, pmg_ppo_stats_device; DESIGN.md
+ * 3.19), validated by the caller.  A table of GAE: element (t, i) at p + t * ts + i * es floats; cut, term and ret may be null. */
+struct PmgGaeTable { const float* p; long long ts, es; };
+struct PmgGae {
+    long long T, N;
+    float gamma, gl;                                    /* gl = gamma * lambda, formed by the caller */
+    PmgGaeTable reward, value, value_next, cut, term;
+    float* adv; long long ats, aes;
+    float* ret; long long rts, res;
+};
+hipError_t pmg_launch_gae(const PmgGae& X, hipStream_t s);
+/* the advantage normaliser over M >= 1 contiguous floats: stats = mean | 1 / (std + eps); apply: y = (x - stats[0]) * stats[1], y may be x */
+struct PmgAdvStats { const float* x; long long M; int ddof; float eps; float* stats; };
+hipError_t pmg_launch_adv_stats(const PmgAdvStats& X, hipStream_t s);
+hipError_t pmg_launch_adv_apply(const float* x, long long M, const float* stats, float* y, hipStream_t s);
+/* the clipped-surrogate head of pmg_launch_ppo_policy_grad: zo [B, 2 A] at zos, n [B, A] at ns, adv [B]; ratio, logratio, clipped and ghead
+ * (at ghs) may be null.  stash / ss: two floats per (row, unit) between the head's two passes -- the actor's delta_{L-1} slot (ss = 2 A) with
+ * grads, else ghead at ghs; null when neither is given (the second pass then does not run). */
+struct PmgPpoPolicy {
+    float pscale, escale, clip_lo, clip_hi, ls_lo, ls_hi;
+    const float* zo; long long zos;
+    const float* n; long long ns;
+    const float* adv;
+    float* ratio; float* logratio; unsigned char* clipped;
+    float* ghead; long long ghs;
+    float* stash; long long ss;
+};
+/* actor.B rows of G.x [B, actor.width[0]]; G carries the actor's arguments as for pmg_launch_sac_policy_grad; Q / T: the chunked reduction
+ * as for pmg_launch_policy_grad, or both null: one chain */
+hipError_t pmg_launch_ppo_policy_grad(const PmgMlp& actor, const PmgGrad& G, const PmgPpoPolicy& X, const PmgGradChunks* Q, const PmgSegs* T, hipStream_t s);
+/* the four means of a minibatch: stats = approximate KL | clip fraction | clipped surrogate | mean log-ratio; B >= 1 */
+struct PmgPpoStats {
+    const float* ratio; const float* logratio; const unsigned char* clipped; const float* adv; long long B;
+    float clip_lo, clip_hi;
+    float* stats;
+};
+hipError_t pmg_launch_ppo_stats(const PmgPpoStats& X, hipStream_t s);
 hipError_t pmg_launch_adam(const PmgSegs& T, const PmgAdam& A, hipStream_t s);
 hipError_t pmg_launch_polyak(const PmgSegs& T, float tau, hipStream_t s);
 /* the data-parallel merge (pmg_mlp_params_pack_device, pmg_mlp_params_merge_device, pmg_mlp_adam_merge_device), validated by

@@ -1945,3 +1945,206 @@ hipError_t pmg_launch_sac_alpha(const PmgSacAlpha& X, hipStream_t s)
     hipLaunchKernelGGL(pmg_k_sac_alpha, dim3(1), dim3(256), 0, s, X);
     return hipGetLastError();
 }
+
+/* PPO on whole rollouts (pmg_gae_device, pmg_adv_stats_device, pmg_adv_apply_device, pmg_ppo_policy_grad_device, pmg_ppo_stats_device;
+ * DESIGN.md 3.19).
+ * Generalised advantage estimation: a thread per env runs t = T-1 ... 0 as ONE chain; the loads of a step do not depend on the chain, so the
+ * unrolled loop keeps four steps' loads in flight.  Time-major tables put consecutive envs on consecutive lanes (coalesced); any other layout
+ * is the same code at its strides. */
+__device__ __forceinline__ float gae_at(const PmgGaeTable& a, long long t, long long i) { return a.p[t * a.ts + i * a.es]; }
+__global__ void __launch_bounds__(256) pmg_k_gae(PmgGae X)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= X.N) return;
+    float adv = 0.f;
+#pragma unroll 4
+    for (long long t = X.T - 1; t >= 0; t--) {
+        const float r = gae_at(X.reward, t, i), v = gae_at(X.value, t, i);
+        float nv = gae_at(X.value_next, t, i);
+        if (X.term.p && gae_at(X.term, t, i) != 0.f) nv = 0.f;
+        const bool cut = t == X.T - 1 || (X.cut.p && gae_at(X.cut, t, i) != 0.f);
+        const float delta = fmaf(X.gamma, nv, r) - v;
+        adv = cut ? delta : fmaf(X.gl, adv, delta);
+        X.adv[t * X.ats + i * X.aes] = adv;
+        if (X.ret) X.ret[t * X.rts + i * X.res] = adv + v;
+    }
+}
+hipError_t pmg_launch_gae(const PmgGae& X, hipStream_t s)
+{
+    if (X.T <= 0 || X.N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pmg_k_gae, dim3((unsigned)((X.N + 255) / 256)), dim3(256), 0, s, X);
+    return hipGetLastError();
+}
+/* THE two-level chain of the one-workgroup statistics (pmg_k_adv_stats in double, pmg_k_ppo_stats in float; pmg_k_sac_alpha's shape, K sums
+ * at once): thread t brings the K partial sums p of the elements b = t (mod 256); thread 0 adds the 256 partial sums of each in ascending
+ * order from +0.0 into total (other threads' total is not written).  One barrier; part is free again behind the caller's next one. */
+template <class T, int K>
+__device__ __forceinline__ void chain256(T (*part)[256], int t, const T (&p)[K], T (&total)[K])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) part[k][t] = p[k];
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            T acc = (T)0;
+            for (int i = 0; i < 256; i++) acc = acc + part[k][i];
+            total[k] = acc;
+        }
+    }
+}
+/* mean and 1 / (std + eps) of M floats, accumulated in double: x * x is exact in double, so q's fma is one rounding however it is built */
+__global__ void __launch_bounds__(256) pmg_k_adv_stats(PmgAdvStats X)
+{
+    __shared__ double part[2][256];
+    const int t = (int)threadIdx.x;
+    double p[2] = {0.0, 0.0}, tot[2] = {0.0, 0.0};
+    for (long long b = t; b < X.M; b += 256) {
+        const double x = (double)X.x[b];
+        p[0] = p[0] + x;
+        p[1] = fma(x, x, p[1]);
+    }
+    chain256<double, 2>(part, t, p, tot);
+    if (t == 0) {
+        const double M = (double)X.M, mean = tot[0] / M;
+        const double var = fmax((tot[1] - tot[0] * mean) / (M - (double)X.ddof), 0.0);
+        X.stats[0] = (float)mean;
+        X.stats[1] = (float)(1.0 / (sqrt(var) + (double)X.eps));
+    }
+}
+hipError_t pmg_launch_adv_stats(const PmgAdvStats& X, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_adv_stats, dim3(1), dim3(256), 0, s, X);
+    return hipGetLastError();
+}
+/* y = (x - mean) * inv, the statistics read from device memory; y may be x: an element is read and written by one thread */
+__global__ void __launch_bounds__(256) pmg_k_adv_apply(const float* x, long long M, const float* __restrict__ stats, float* y)
+{
+    const float mean = stats[0], inv = stats[1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256) y[i] = (x[i] - mean) * inv;
+}
+hipError_t pmg_launch_adv_apply(const float* x, long long M, const float* stats, float* y, hipStream_t s)
+{
+    if (M <= 0) return hipSuccess;
+    const long long want = (M + 255) / 256;
+    hipLaunchKernelGGL(pmg_k_adv_apply, dim3((unsigned)(want < (1 << 20) ? want : (1 << 20))), dim3(256), 0, s, x, M, stats, y);
+    return hipGetLastError();
+}
+/* PPO's actor update in one call (pmg_ppo_policy_grad_device), pmg_k_sac_policy_grad_rows' sibling without critics: gather, the actor's
+ * layers (mlp_layers_saved), the clipped-surrogate head in two passes of pmg_k_sac's (row, unit j < A) map with the row's sum between them,
+ * the actor's transposed layers, then the weights kernel of 3.11 (or the partials / merge pair of 3.12), unchanged, on the actor's workspace.
+ * Ownership.  The tile holds z: means in columns [0, A), raw log-stds in [A, 2 A).  In BOTH passes the thread of (row, unit j) touches columns
+ * j and A + j of its row and no other (another unit j' of the row touches j' and A + j', and j' != j, A + j' != j as j < A), so neither pass
+ * needs a barrier inside.  Pass 1 reads m and the raw log-std, puts the summand ln_j - lo_j of the log-ratio into column j and LEAVES the raw
+ * log-std in column A + j (pass 2 takes the clamp's predicate from it); w and isd go to X.stash, two floats per (row, unit) -- the actor's
+ * delta_{L-1} slot, or d_ghead without grads -- where the SAME thread reads them back in pass 2 and overwrites them with g_mu | g_ls: a thread
+ * reads only its own earlier stores, so no ordering between threads is involved.
+ * Barriers.  The one behind pass 1 orders every summand before the sum of the row's thread (t < 32), which writes the row's k into rowk[t],
+ * LDS beside the tile.  The one behind the sum orders (a) the sum's reads of columns [0, A) before the hand-back of g_mu into them and (b) rowk
+ * before its readers.  The one behind pass 2 orders g_mu | g_ls in columns [0, 2 A) before the actor's first transposed chain, and the closing
+ * one everything before the next tile's gather (and rowk's readers before its next writers).
+ * Stale tile.  Pass 2 writes columns [0, 2 A) of ALL 32 rows, +0.0 in the rows past the batch (pass 1 leaves those rows alone: nothing reads
+ * them); 2 A is even, so the first transposed chain reads no padding column, and whatever a wider hidden layer left beyond 2 A is not read:
+ * mlp_backward's own write-backs cover whole strips from there on. */
+__global__ void __launch_bounds__(256, 2) pmg_k_ppo_policy_grad_rows(PmgMlp P, PmgGrad G, PmgPpoPolicy X)
+{
+    __shared__ float tile[MLP_ROWS * MLP_LD];
+    __shared__ float rowk[MLP_ROWS];                             /* k of row r of the tile, written by its thread between the passes */
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31;
+    const int Dx = P.width[0], A = P.width[P.L] >> 1;
+    const MlpRawRows S = {G.x, G.xs};
+    const bool second = X.stash != nullptr;                      /* g_mu | g_ls are wanted: d_ghead or grads */
+    const long long ntiles = (P.B + MLP_ROWS - 1) / MLP_ROWS;
+    for (long long tb = blockIdx.x; tb < ntiles; tb += gridDim.x) {
+        const long long row0 = tb * MLP_ROWS;
+        mlp_gather(tile, S, row0, P.B, Dx, (Dx + 1) & ~1, t);
+        __syncthreads();
+        unsigned int m1 = 0, m2 = 0, m3 = 0;
+        mlp_layers_saved(tile, P, G, row0, lane, wave, col, m1, m2, m3);
+        for (int i = t; i < MLP_ROWS * A; i += 256) {            /* pass 1: both policies at the recorded u */
+            const int r = i / A, j = i - r * A;
+            const long long row = row0 + r;
+            if (row >= P.B) break;
+            const float m = tile[r * MLP_LD + j], ls = fminf(fmaxf(tile[r * MLP_LD + A + j], X.ls_lo), X.ls_hi);
+            const float n = X.n[row * X.ns + j], lso = fminf(fmaxf(X.zo[row * X.zos + A + j], X.ls_lo), X.ls_hi);
+            const float u = fmaf(expf(lso), n, X.zo[row * X.zos + j]);   /* sac_head's u */
+            const float lo = fmaf(-0.5f * n, n, -lso);
+            const float isd = expf(-ls), w = (u - m) * isd;
+            const float ln = fmaf(-0.5f * w, w, -ls);
+            tile[r * MLP_LD + j] = ln - lo;
+            if (second) { X.stash[row * X.ss + j] = w; X.stash[row * X.ss + A + j] = isd; }
+        }
+        __syncthreads();                                         /* every summand of the tile is written */
+        if (t < MLP_ROWS && row0 + t < P.B) {
+            const long long row = row0 + t;
+            const float lr = sac_logp(tile, t, A), rho = expf(lr), adv = X.adv[row];
+            const bool clipped = (adv > 0.f && rho > X.clip_hi) || (adv < 0.f && rho < X.clip_lo);
+            rowk[t] = clipped ? 0.f : (X.pscale * adv) * rho;
+            if (X.ratio) X.ratio[row] = rho;
+            if (X.logratio) X.logratio[row] = lr;
+            if (X.clipped) X.clipped[row] = clipped ? 1 : 0;
+        }
+        if (second) {
+            __syncthreads();                                     /* the sums are read: columns [0, A) are free; rowk is written */
+            for (int i = t; i < MLP_ROWS * A; i += 256) {        /* pass 2: the hand-back, all 32 rows */
+                const int r = i / A, j = i - r * A;
+                const long long row = row0 + r;
+                float gm = 0.f, gl = 0.f;
+                if (row < P.B) {
+                    const float k = rowk[r], w = X.stash[row * X.ss + j], isd = X.stash[row * X.ss + A + j], raw = tile[r * MLP_LD + A + j];
+                    gm = k * (w * isd);
+                    gl = (raw >= X.ls_lo && raw <= X.ls_hi) ? fmaf(k, fmaf(w, w, -1.f), X.escale) : 0.f;
+                    if (X.ghead) { X.ghead[row * X.ghs + j] = gm; X.ghead[row * X.ghs + A + j] = gl; }
+                    /* with grads the stash IS the actor's delta_{L-1} slot: the stores stay behind the loads above */
+                    if (G.grads) { X.stash[row * X.ss + j] = gm; X.stash[row * X.ss + A + j] = gl; }
+                }
+                tile[r * MLP_LD + j] = gm;
+                tile[r * MLP_LD + A + j] = gl;
+            }
+            if (G.grads) {
+                __syncthreads();
+                mlp_backward(tile, P, G, row0, lane, wave, col, m1, m2, m3);
+            }
+        }
+        __syncthreads();                                         /* the next tile's rows overwrite this one's */
+    }
+}
+hipError_t pmg_launch_ppo_policy_grad(const PmgMlp& P, const PmgGrad& G, const PmgPpoPolicy& X, const PmgGradChunks* C, const PmgSegs* T, hipStream_t s)
+{
+    if (P.B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pmg_k_ppo_policy_grad_rows, dim3(mlp_grid(P.B)), dim3(256), 0, s, P, G, X);
+    if (G.grads) {
+        const MlpRawRows S = {G.x, G.xs};
+        if (!C) hipLaunchKernelGGL((pmg_k_mlp_grad_weights<MlpRawRows>), dim3(pmg_grad_w_tiles(P)), dim3(64), 0, s, S, P, G);
+        else {
+            hipLaunchKernelGGL((pmg_k_mlp_grad_partials<MlpRawRows>), dim3((unsigned)(C->C * C->tiles)), dim3(64), 0, s, S, P, G, *C);
+            hipLaunchKernelGGL(pmg_k_mlp_grad_merge, dim3(seg_grid(*T)), dim3(256), 0, s, *T, (const float*)C->part, C->C, C->P);
+        }
+    }
+    return hipGetLastError();
+}
+/* the four means a PPO learner logs (pmg_ppo_stats_device): chain256 in float, the quotients in double as pmg_k_sac_alpha forms its own */
+__global__ void __launch_bounds__(256) pmg_k_ppo_stats(PmgPpoStats X)
+{
+    __shared__ float part[4][256];
+    const int t = (int)threadIdx.x;
+    float p[4] = {0.f, 0.f, 0.f, 0.f}, tot[4] = {0.f, 0.f, 0.f, 0.f};
+    for (long long b = t; b < X.B; b += 256) {
+        const float rho = X.ratio[b], lr = X.logratio[b], adv = X.adv[b];
+        const float cr = fminf(fmaxf(rho, X.clip_lo), X.clip_hi);
+        p[0] = p[0] + ((rho - 1.f) - lr);
+        p[1] = p[1] + (X.clipped[b] ? 1.f : 0.f);
+        p[2] = p[2] + fminf(rho * adv, cr * adv);
+        p[3] = p[3] + lr;
+    }
+    chain256<float, 4>(part, t, p, tot);
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) X.stats[k] = (float)((double)tot[k] / (double)(float)X.B);
+    }
+}
+hipError_t pmg_launch_ppo_stats(const PmgPpoStats& X, hipStream_t s)
+{
+    hipLaunchKernelGGL(pmg_k_ppo_stats, dim3(1), dim3(256), 0, s, X);
+    return hipGetLastError();
+}

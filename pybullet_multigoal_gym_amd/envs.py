@@ -304,6 +304,15 @@ class KukaVecEnv:
         return self._gaussian_actor
 
     @property
+    def ppo(self):
+        """The PPO calls of this env's device (ppo.Ppo): advantage estimation and normalisation over a rollout, the clipped-surrogate gradient
+        of ``gaussian_actor`` and the minibatch statistics, created on first use."""
+        if getattr(self, '_ppo', None) is None:
+            from .ppo import Ppo
+            self._ppo = Ppo(self)
+        return self._ppo
+
+    @property
     def critic(self):
         """The critic network of this env's learner on the device (critic.Critic): Q(x, a) and fused TD targets, created on first
         access."""
