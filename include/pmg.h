@@ -61,11 +61,17 @@ enum {
                             prone list [N], free list [N], n_redo, redo list [N], then the two-pass plan's per-workgroup class
                             counts and its promotion flag -- the layout is defined in pybullet_multigoal_gym_amd/csrc/pmg_sched.h
                             (pmgx::Sched); see DESIGN.md 3.2 */
-    PMG_BUF_ENV_CYCLES = 10 /* [N, 2] int32: shader cycles / 64 the env's wavefront spent in its last step, and the largest contact
+    PMG_BUF_ENV_CYCLES = 10, /* [N, 2] int32: shader cycles / 64 the env's wavefront spent in its last step, and the largest contact
                             count any of that step's substeps saw (envs with free objects).  Kept when the handle was created with
                             PMG_ENV_CYCLES=1 in the environment (diagnostics) AND whenever the longest-first order of the fast-path
                             list is on (block_stack and the chest tasks from 4096 envs, PMG_LPT_CYCLES; the plan's predictor: 8 B per
                             env written every step); PMG_E_INVALID otherwise */
+    PMG_BUF_WAVE_TRACE = 11 /* [2 N] records of 64 bytes, one per wavefront of the last reach step (tip control) and its redo pass: start
+                            and end on the constant-rate clock and on the shader clock (4 x int64), HW_ID, XCC_ID (uint32), role (0 list-0
+                            wavefront 0, 1 list-0 helper, 2 packed, 3 redo), env (the first of a packed wavefront's four), largest contact
+                            count, kernel (1 pmg_k_step_reach, 2 pmg_k_step_reach2, 3 pmg_k_redo), two unused words; unused records are all
+                            0xFF bytes.  Kept when the handle was created with PMG_WAVE_TRACE=1 in the environment (diagnostics,
+                            tools/wave_trace.py; PMG_BUF_ENV_CYCLES exists then too); PMG_E_INVALID otherwise */
 };
 
 /* POD configuration; mirrors the kwargs of pmg.make_env (P/__init__.py:4-11)

@@ -17,6 +17,11 @@ PMG_BUF_PACKED = 7
 PMG_BUF_STATE = 8
 PMG_BUF_SCHED = 9
 PMG_BUF_ENV_CYCLES = 10
+PMG_BUF_WAVE_TRACE = 11
+# one record of PMG_BUF_WAVE_TRACE (include/pmg.h; pmgx::WaveRec of csrc/pmg_kernels.h), 64 bytes
+WAVE_REC = np.dtype([('t0', '<i8'), ('t1', '<i8'), ('c0', '<i8'), ('c1', '<i8'), ('hw', '<u4'), ('xcc', '<u4'), ('role', '<i4'),
+                     ('env', '<i4'), ('nc', '<i4'), ('kernel', '<i4'), ('pad', '<i4', (2,))])
+WAVE_ROLES = ('wave0', 'helper', 'packed', 'redo')
 PMG_NORM_OBSERVATION = 0
 PMG_NORM_POLICY_STATE = 1
 PMG_NORM_GOAL = 2
@@ -371,6 +376,14 @@ class PmgHandle:
         buf = np.empty((self.N, 2), np.int32)
         self.sync()
         self.download(buf, self.device_ptr(PMG_BUF_ENV_CYCLES))
+        return buf
+
+    def wave_trace(self):
+        """Per-wavefront records of the last reach step (diagnostics; the handle must have been created with PMG_WAVE_TRACE=1 in the
+        environment): [2 N] WAVE_REC; a record no wavefront wrote is all 0xFF bytes (role == -1)."""
+        buf = np.empty(2 * self.N, WAVE_REC)
+        self.sync()
+        self.download(buf, self.device_ptr(PMG_BUF_WAVE_TRACE))
         return buf
 
     def stream(self):

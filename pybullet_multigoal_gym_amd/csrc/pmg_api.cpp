@@ -134,6 +134,7 @@ struct pmg_env {
     bool ever_reset = false;
     int packed = 1;                   /* reach: contact-free envs four per wavefront (PMG_PACKED=0 switches it off) */
     int two_wave = 1;                 /* reach: the two-wavefront kernel for steps with contact-prone envs (PMG_REACH_TWO_WAVES=0: never) */
+    pmgx::WaveRec* wave_trace = nullptr;   /* PMG_WAVE_TRACE=1 at creation: [2 N] records of the reach step's wavefronts (PMG_BUF_WAVE_TRACE) */
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     /* overlapped all-gather (pmg_comm_overlap): the packed rows are double-buffered -- step t writes out2[t & 1], its all-gather
@@ -459,7 +460,15 @@ int pmg_create(const pmg_config* cfg, pmg_env** out)
             CREATE_TRY(hipMalloc((void**)&e->P.lpt_state, (2 + pmg::LPT_BINS) * sizeof(int)));
             CREATE_TRY(hipMemset(e->P.lpt_state, 0, (2 + pmg::LPT_BINS) * sizeof(int)));
         }
-        if ((ec && atoi(ec) != 0) || ((e->P.lpt_thresh > 0 || e->P.lpt_permille > 0) && e->nb > 1)) {
+        /* PMG_WAVE_TRACE=1 (diagnostics): one record per wavefront of the reach step kernels and the redo pass, 2 N of them, filled with
+         * 0xFF bytes in front of every step; the records take their contact counts from env_cycles, which is kept with them */
+        const char* wt = getenv("PMG_WAVE_TRACE");
+        const bool trace = wt && atoi(wt) != 0;
+        if (trace) {
+            CREATE_TRY(hipMalloc((void**)&e->wave_trace, 2 * N * sizeof(pmgx::WaveRec)));
+            CREATE_TRY(hipMemset(e->wave_trace, 0xFF, 2 * N * sizeof(pmgx::WaveRec)));
+        }
+        if (trace || (ec && atoi(ec) != 0) || ((e->P.lpt_thresh > 0 || e->P.lpt_permille > 0) && e->nb > 1)) {
             CREATE_TRY(hipMalloc((void**)&e->P.env_cycles, 2 * N * sizeof(int)));
             CREATE_TRY(hipMemset(e->P.env_cycles, 0, 2 * N * sizeof(int)));
         }
@@ -514,7 +523,7 @@ int pmg_create(const pmg_config* cfg, pmg_env** out)
     {   /* the tuning / experiment switches this library reads from the environment change its schedule (never its results' meaning):
          * a stray one in a user's shell -- PMG_PACKED=0 halves the throughput -- must not go unnoticed: ONE line on stderr per handle */
         static const char* const kSwitches[] = {"PMG_PACKED", "PMG_REACH_TWO_WAVES", "PMG_NEAR_R", "PMG_CHEST_REACH", "PMG_FD_DIV", "PMG_WAVE_BUDGET",
-                                                "PMG_LPT_CYCLES", "PMG_LPT_PERMILLE", "PMG_ENV_CYCLES", "PMG_LIST0_PRIO", "PMG_LIST0_FIRST", "PMG_PLAN_TWO_PASS",
+                                                "PMG_LPT_CYCLES", "PMG_LPT_PERMILLE", "PMG_ENV_CYCLES", "PMG_WAVE_TRACE", "PMG_LIST0_PRIO", "PMG_LIST0_FIRST", "PMG_PLAN_TWO_PASS",
                                                 "PMG_REWARD_GENERIC"};
         std::string active;
         for (const char* name : kSwitches)
@@ -536,7 +545,7 @@ void pmg_destroy(pmg_env* e)
     (void)hipFree(e->P.curr); (void)hipFree(e->P.blocks); (void)hipFree(e->P.rng);
     if (e->out2[1]) { (void)hipFree(e->out2[0]); (void)hipFree(e->out2[1]); }
     else (void)hipFree(e->P.out);
-    (void)hipFree(e->P.sched); (void)hipFree(e->P.env_cycles); (void)hipFree(e->P.lpt_state);
+    (void)hipFree(e->P.sched); (void)hipFree(e->P.env_cycles); (void)hipFree(e->wave_trace); (void)hipFree(e->P.lpt_state);
     (void)hipFree(e->d_actions); (void)hipFree(e->d_mask);
     for (int w = 0; w < 3; w++) (void)hipFree(e->norm[w].tot);
     for (Scratch* b : {&e->st_a, &e->st_b, &e->st_out, &e->st_flag, &e->her_idx, &e->norm_gather}) b->release();
@@ -630,8 +639,9 @@ int pmg_step_device(pmg_env* e, const float* d_actions)
     /* reach: steps that have contact-prone envs run the two-wavefront kernel while the contact-free list is at most one
      * wavefront per SIMD (pmg_kernels.hip); mode 2 launches both kernels and the DEVICE picks one by the plan's count */
     if (e->packed && e->nb == 0 && !e->cfg.joint_control && e->two_wave && e->dims.num_envs <= (e->P.wave_budget / 6) * 16) mode = 2;
+    if (e->wave_trace) HIP_TRY(e, hipMemsetAsync(e->wave_trace, 0xFF, 2 * (size_t)e->dims.num_envs * sizeof(pmgx::WaveRec), e->stream));
     if (timed) HIP_TRY(e, hipEventRecord(e->ev_a[i], e->stream));
-    HIP_TRY(e, pmg_launch_step(e->P, d_actions, e->stream, mode, e->side, e->ev_fork, e->ev_join));
+    HIP_TRY(e, pmg_launch_step(e->P, d_actions, e->stream, mode, e->side, e->ev_fork, e->ev_join, e->wave_trace));
     if (timed) HIP_TRY(e, hipEventRecord(e->ev_b[i], e->stream));
     return PMG_OK;
 }
@@ -692,6 +702,9 @@ int pmg_device_ptr(pmg_env* e, int which, void** d_ptr)
     case PMG_BUF_ENV_CYCLES:
         if (!e->P.env_cycles) return fail(e, PMG_E_INVALID, "pmg_device_ptr: PMG_BUF_ENV_CYCLES is kept only with PMG_ENV_CYCLES=1 in the environment at pmg_create, or with the longest-first order on (PMG_LPT_CYCLES)");
         *d_ptr = e->P.env_cycles; return PMG_OK;
+    case PMG_BUF_WAVE_TRACE:
+        if (!e->wave_trace) return fail(e, PMG_E_INVALID, "pmg_device_ptr: PMG_BUF_WAVE_TRACE is kept only with PMG_WAVE_TRACE=1 in the environment at pmg_create");
+        *d_ptr = e->wave_trace; return PMG_OK;
     default: return fail(e, PMG_E_INVALID, "pmg_device_ptr: buffer %d is not a device buffer (use PMG_BUF_PACKED + pmg_dims offsets)", which);
     }
 }

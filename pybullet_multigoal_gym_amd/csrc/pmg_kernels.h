@@ -9,6 +9,16 @@
 #include "pmg_contact.h"
 #include "pmg_sched.h"
 
+#ifndef PMG_REACH_HELPER_WAVE
+/* reach, two-wavefront workgroups: the helper is THIS wavefront of the workgroup and the env's dynamics -- the step's long chain -- the
+ * other one.  0 since round 10: in a contact step of the 4096-env headline the dispatcher gives the SIMD of a list-0 workgroup's FIRST
+ * wavefront a packed wavefront as well in seven cases of eight, and never the SIMD of its second one (wavefront trace,
+ * profiles/r10_reach_contact_step.txt).  With the dynamics on wavefront 0 that partner ran 0.81 ms instead of 0.47 and ended the step
+ * 25 us behind the slowest contact env; beside the helper, which idles through the solve phase, it is through in time and the contact
+ * env's own wavefront ends the step: 0.794 -> 0.774 ms, 5.06 -> 5.19 M env-steps/s.  Same device functions, same lanes, the same two
+ * barriers per substep on either side: nothing but which of the two wavefronts takes which branch (1: the layout of rounds 3-9) */
+#define PMG_REACH_HELPER_WAVE 0
+#endif
 #ifndef PMG_COLD_CONTACTS
 #define PMG_COLD_CONTACTS 1 /* keep the reach kernel's rare contact phases out of line (compact hot loop) */
 #endif
@@ -16,6 +26,24 @@
 /* kernel parameters: a namespace of its own, so that argument-dependent lookup never mixes the two lane-layout
  * namespaces (pmg / pmgp) that both take it */
 namespace pmgx {
+/* PMG_WAVE_TRACE (diagnostics): what one wavefront of a reach step leaves behind, 64 bytes; tools/wave_trace.py reads them.
+ * The buffer holds 2 N records, filled with 0xFF bytes in front of every step; record of
+ *   workgroup b, wavefront w of list 0 (b < n0):   2 b + w       (pmg_k_step_reach's one-wavefront workgroups: 2 b)
+ *   packed wavefront g (4 g < n1):                 2 n0 + g      (either kernel)
+ *   workgroup b of the redo pass:                  2 N - 1 - b
+ * -- at most 2 n0 + ceil(n1 / 4) + n1 <= 2 N of them, so no two wavefronts share one */
+struct WaveRec {
+    long long t0, t1;       /* constant-rate clock (trace_wall_clock) at the wavefront's first and last instructions */
+    long long c0, c1;       /* shader clock (wv::cycles) at the same two places */
+    unsigned hw, xcc;       /* HW_ID / XCC_ID (trace_hw_ids) */
+    int role;               /* WAVE_ROLE_* */
+    int env;                /* the env, or the first env of a packed wavefront */
+    int nc;                 /* largest contact count of the env's substeps (wavefront 0 and redo; the packed path has none; helper: -1) */
+    int kernel;             /* 1 pmg_k_step_reach, 2 pmg_k_step_reach2, 3 pmg_k_redo */
+    int pad[2];
+};
+static_assert(sizeof(WaveRec) == 64, "tools/wave_trace.py and _lib.py read 64-byte records");
+enum { WAVE_ROLE_WAVE0 = 0, WAVE_ROLE_HELPER = 1, WAVE_ROLE_PACKED = 2, WAVE_ROLE_REDO = 3 };
 struct EnvParams {
     int n_envs, task, nb, grasping, has_obj, joint_control, binary_reward, max_steps, in_air, random_order;
     int multi;              /* multi-block observation layout: block_stack / block_rearrange */
@@ -58,6 +86,67 @@ struct EnvParams {
 #endif
     __host__ __device__ __forceinline__ Sched schedule() const { return Sched{sched, n_envs}; }
 };
+/* what the trace reads besides the shader clock: the constant-rate clock (s_memrealtime, 100 MHz: one time base for wavefronts on
+ * different SIMDs, CUs and XCDs) and where the wavefront runs -- HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13])
+ * and XCC_ID [3:0].  The CPU emulator runs one workgroup at a time: it "sits" on CU blockIdx % 16, its wavefronts on SIMDs 0, 1, ... */
+#ifdef PMG_EMULATE
+inline long long trace_wall_clock() { static long long t = 0; return t += 1; }
+inline void trace_hw_ids(unsigned& hw, unsigned& xcc) { hw = ((blockIdx.x & 15u) << 8) | ((((unsigned)threadIdx.x >> 6) & 3u) << 4); xcc = (blockIdx.x >> 4) & 7u; }
+#else
+__device__ __forceinline__ long long trace_wall_clock() { return (long long)wall_clock64(); }
+__device__ __forceinline__ void trace_hw_ids(unsigned& hw, unsigned& xcc)
+{
+    hw = 0u; xcc = 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+#endif
+}
+#endif
+/* One half of a wavefront's trace record, by its first lane with ordinary vector stores: `end` = false at the wavefront's first
+ * instruction (start clocks, placement, role, env), true at its last (end clocks, contact count).  Two halves, and the record
+ * found again at the exit from what the kernel has anyway, so that NOTHING of the trace is carried through the step: a start
+ * time kept in registers would sit in the allocation of the substep loop whether the switch is on or off. */
+__device__ __forceinline__ void wave_trace_write(WaveRec* trace, const EnvParams& P, int slot, int role, int env, int kernel, bool end)
+{
+    if (((int)threadIdx.x & 63) != 0 || slot < 0 || slot >= 2 * P.n_envs) return;
+    WaveRec* r = trace + slot;
+    if (!end) {
+        unsigned hw, xcc;
+        trace_hw_ids(hw, xcc);
+        r->hw = hw; r->xcc = xcc; r->role = role; r->env = env; r->kernel = kernel;
+        r->c0 = wv::cycles();
+        r->t0 = trace_wall_clock();
+    } else {
+        r->t1 = trace_wall_clock();
+        r->c1 = wv::cycles();
+        r->nc = (role == WAVE_ROLE_WAVE0 || role == WAVE_ROLE_REDO) ? P.env_cycles[2 * env + 1] : (role == WAVE_ROLE_PACKED ? 0 : -1);
+    }
+}
+/* pmg_k_step_reach (one-wavefront workgroups: list 0 one env each, then the packed groups) */
+__device__ __forceinline__ void wave_trace_reach(WaveRec* trace, const EnvParams& P, bool end)
+{
+    if (!trace) return;
+    const Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0), g = b - n0;
+    if (b < n0) wave_trace_write(trace, P, 2 * b, WAVE_ROLE_WAVE0, S.at(0, b), 1, end);
+    else if (4 * g < S.count(1)) wave_trace_write(trace, P, 2 * n0 + g, WAVE_ROLE_PACKED, S.at(1, 4 * g), 1, end);
+}
+/* pmg_k_step_reach2 (two-wavefront workgroups: list 0 = the env's dynamics + its helper, then pairs of packed groups) */
+__device__ __forceinline__ void wave_trace_reach2(WaveRec* trace, const EnvParams& P, bool end)
+{
+    if (!trace) return;
+    const Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0), w = (int)threadIdx.x >> 6, g = 2 * (b - n0) + w;
+    if (b < n0) wave_trace_write(trace, P, 2 * b + w, w == PMG_REACH_HELPER_WAVE ? WAVE_ROLE_HELPER : WAVE_ROLE_WAVE0, S.at(0, b), 2, end);
+    else if (4 * g < S.count(1)) wave_trace_write(trace, P, 2 * n0 + g, WAVE_ROLE_PACKED, S.at(1, 4 * g), 2, end);
+}
+__device__ __forceinline__ void wave_trace_redo(WaveRec* trace, const EnvParams& P, bool end)
+{
+    if (!trace) return;
+    const Sched S = P.schedule();
+    wave_trace_write(trace, P, 2 * P.n_envs - 1 - (int)blockIdx.x, WAVE_ROLE_REDO, S.redo_env(blockIdx.x), 3, end);
+}
 }  // namespace pmgx
 
 namespace pmg {

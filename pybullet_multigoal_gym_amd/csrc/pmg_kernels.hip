@@ -41,6 +41,11 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) pmg_k_step(pmg::EnvParam
 #define PMG_REACH_VGPRS
 #endif
 __device__ __forceinline__ bool two_wave_step(int n_prone, int n_envs) { return n_prone > 0; }
+/* Each of the three reach kernels has a traced twin (PMG_WAVE_TRACE=1 at pmg_create; launched INSTEAD of it, chosen on the host by the
+ * handle's trace buffer): every live wavefront writes half of its record on its way in and the other half on its way out
+ * (pmgx::wave_trace_*).  Twins and not a pointer test inside one kernel: with the test the register allocation of the whole kernel
+ * came out differently (thousands of changed lines in the substep loop of all three), so the kernels that run with the switch off are
+ * compiled without any of it and stay instruction for instruction what they were. */
 __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_step_reach(pmg::EnvParams P, const float* __restrict__ actions, int defer)
 {
     const pmgx::Sched S = P.schedule();
@@ -49,9 +54,21 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_st
     if (b < n0) pmg::step_env<0, 8, false>(P, actions, S.at(0, b));
     else pmgp::step_group(P, actions, b - n0);
 }
+__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_step_reach_traced(pmg::EnvParams P, const float* __restrict__ actions, int defer, pmgx::WaveRec* trace)
+{
+    const pmgx::Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0);
+    if (defer && two_wave_step(n0, P.n_envs)) return;
+    pmgx::wave_trace_reach(trace, P, false);
+    if (b < n0) pmg::step_env<0, 8, false>(P, actions, S.at(0, b));
+    else pmgp::step_group(P, actions, b - n0);
+    pmgx::wave_trace_reach(trace, P, true);
+}
 /* The same with TWO wavefronts per workgroup, for steps that have contact-prone envs (a batched step lasts as long as
- * its slowest wavefront, and that is one of them): on the contact-prone list wavefront 1 runs the narrowphase of every
- * substep beside wavefront 0's dynamics (helper_wave_loop: 32 k -> 27 k cycles per substep with both fingers on the
+ * its slowest wavefront, and that is one of them): on the contact-prone list one wavefront (PMG_REACH_HELPER_WAVE: the
+ * workgroup's first, so that the packed wavefront the dispatcher puts beside a list-0 workgroup's first wavefront sits beside the
+ * helper and not beside the long chain) runs the narrowphase of every
+ * substep beside the other one's dynamics (helper_wave_loop: 32 k -> 27 k cycles per substep with both fingers on the
  * table); on the contact-free list both wavefronts carry four envs each, so that no wavefront of the launch idles.
  * 4096 envs, staggered episodes: 1.34 -> 1.20 ms per batched step.  A batch WITHOUT contact-prone envs is better off
  * with one-wavefront workgroups (the dispatcher places 1024 of them exactly one per SIMD: 0.54 ms; 512 two-wave ones:
@@ -70,6 +87,16 @@ __global__ void __launch_bounds__(128, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_s
     if (b < n0) pmg::step_env<0, 8, false, true>(P, actions, S.at(0, b));
     else pmgp::step_group(P, actions, 2 * (b - n0) + ((int)threadIdx.x >> 6));
 }
+__global__ void __launch_bounds__(128, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_step_reach2_traced(pmg::EnvParams P, const float* __restrict__ actions, pmgx::WaveRec* trace)
+{
+    const pmgx::Sched S = P.schedule();
+    const int b = (int)blockIdx.x, n0 = S.count(0);
+    if (!two_wave_step(n0, P.n_envs)) return;
+    pmgx::wave_trace_reach2(trace, P, false);
+    if (b < n0) pmg::step_env<0, 8, false, true>(P, actions, S.at(0, b));
+    else pmgp::step_group(P, actions, 2 * (b - n0) + ((int)threadIdx.x >> 6));
+    pmgx::wave_trace_reach2(trace, P, true);
+}
 /* The redo pass: one workgroup per env of the redo list recomputes it from its untouched state with the full kernel of its task;
  * the grid is sized for the worst case and its surplus workgroups leave on their first load */
 /* reach: envs the packed path gave up on (a finger reached the table although the plan said it would not) */
@@ -78,6 +105,14 @@ __global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_re
     const pmgx::Sched S = P.schedule();
     if ((int)blockIdx.x >= S.redo_count()) return;
     pmg::step_env<0, 8, false>(P, actions, S.redo_env(blockIdx.x));
+}
+__global__ void __launch_bounds__(64, PMG_WAVES_PER_EU) PMG_REACH_VGPRS pmg_k_redo_traced(pmg::EnvParams P, const float* __restrict__ actions, pmgx::WaveRec* trace)
+{
+    const pmgx::Sched S = P.schedule();
+    if ((int)blockIdx.x >= S.redo_count()) return;
+    pmgx::wave_trace_redo(trace, P, false);
+    pmg::step_env<0, 8, false>(P, actions, S.redo_env(blockIdx.x));
+    pmgx::wave_trace_redo(trace, P, true);
 }
 /* free objects: <1, 24, CYL> an env with more than 12 contacts on a packed row, <5, 48, 0> / <6, 48, CYL> (chest tasks) an env of list 1
  * whose 30-contact store, or whose ranked stage slots, overflowed */
@@ -216,7 +251,7 @@ static void launch_redo(const pmg::EnvParams& P, const float* d_actions, hipStre
  * (pmg_step*: PMG_ERR_HIP + pmg_last_error) */
 #define PMG_FJ(call) do { hipError_t fj_e_ = (call); if (fj_e_ != hipSuccess) return fj_e_; } while (0)
 hipError_t pmg_launch_step(const pmg::EnvParams& P, const float* d_actions, hipStream_t s, int packed, hipStream_t side,
-                           hipEvent_t ev_fork, hipEvent_t ev_join)
+                           hipEvent_t ev_fork, hipEvent_t ev_join, pmgx::WaveRec* trace)
 {
     /* Which of the two concurrent launches is submitted first.  list0_first: the full-store list -- the step's long
      * wavefronts -- goes to the main stream at once and the fast-path list follows on the side stream behind the fork event
@@ -260,7 +295,14 @@ hipError_t pmg_launch_step(const pmg::EnvParams& P, const float* d_actions, hipS
         /* the one-wavefront kernel FIRST: when it is its turn (a contact-free step) its 1024 wavefronts are placed on an
          * empty machine, one per SIMD; behind the other kernel's draining empty workgroups they were not (0.82 ms) */
         /* n_prone + ceil(n_free / 4) <= N workgroups; deferring (packed == 2) it runs on contact-free steps only: ceil(N / 4) */
-        hipLaunchKernelGGL(pmg_k_step_reach, dim3(packed == 2 ? (P.n_envs + 3) / 4 : P.n_envs), dim3(64), 0, s, P, d_actions, packed == 2 ? 1 : 0);
+        const dim3 g1(packed == 2 ? (P.n_envs + 3) / 4 : P.n_envs);
+        if (trace) {   /* PMG_WAVE_TRACE=1: the traced twins, same grids */
+            hipLaunchKernelGGL(pmg_k_step_reach_traced, g1, dim3(64), 0, s, P, d_actions, packed == 2 ? 1 : 0, trace);
+            if (packed == 2) hipLaunchKernelGGL(pmg_k_step_reach2_traced, dim3(P.n_envs), dim3(128), 0, s, P, d_actions, trace);
+            hipLaunchKernelGGL(pmg_k_redo_traced, dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions, trace);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL(pmg_k_step_reach, g1, dim3(64), 0, s, P, d_actions, packed == 2 ? 1 : 0);
         if (packed == 2) hipLaunchKernelGGL(pmg_k_step_reach2, dim3(P.n_envs), dim3(128), 0, s, P, d_actions);   /* n_prone + ceil(n_free / 8) <= N */
         /* mispredictions are rare; surplus workgroups of the redo grid exit on their first instruction */
         hipLaunchKernelGGL(pmg_k_redo, dim3(redo_grid(P.n_envs)), dim3(64), 0, s, P, d_actions);

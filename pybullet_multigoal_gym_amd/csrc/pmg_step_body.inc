@@ -1393,8 +1393,7 @@ __device__ __forceinline__ bool substep(const EnvParams& P, ContactLds<NB, MAXC>
         if (NB > 0 && MAXC < (NB == 1 ? 24 : 48) && nc > MAXC) return false;   /* (fast-path store: see above) */
         if (nc > MAXC) nc = MAXC;
     }
-    ncmax = nc > ncmax ? nc : ncmax;                        /* (diagnostics: PMG_ENV_CYCLES) */
-    /* reach, one env per wavefront: lanes 16..39 are free, the contact rows are built and solved in row space */
+    ncmax = nc > ncmax ? nc : ncmax;                        /* (diagnostics: PMG_ENV_CYCLES) */    /* reach, one env per wavefront: lanes 16..39 are free, the contact rows are built and solved in row space */
     const bool rowspace = PMG_ROWSPACE && NB == 0 && WV::LANES == 64 && MAXC <= 8 && mc.fast;
     /* one free object, one env per wavefront: the same for up to OBJ_ROWSPACE_MAXC contacts (lanes 16..63 = 48 rows) */
     const bool rowspace1 = PMG_ROWSPACE && NB == 1 && WV::LANES == 64 && mc.fast && nc > 0 && nc <= OBJ_ROWSPACE_MAXC;
@@ -1554,6 +1553,10 @@ __device__ __forceinline__ bool substep(const EnvParams& P, ContactLds<NB, MAXC>
 /* `live` = this env's results are to be stored (false for the shadow rows of a partly filled packed wavefront);
  * returns false when the packed path gave up on the env (more contacts than its small LDS row store holds): nothing
  * has been written then and the caller queues the env for the one-env-per-wavefront kernel */
+/* which wavefront of a two-wavefront workgroup is the helper (the other one carries the env's dynamics): PMG_REACH_HELPER_WAVE for
+ * reach, wavefront 1 on the tasks with objects (slide's third wavefront is always wavefront 2) */
+template <int NB, bool SPEC>
+__device__ __forceinline__ constexpr int helper_wave_index() { return (NB == 0 && !SPEC) ? PMG_REACH_HELPER_WAVE : 1; }
 template <int NB, int MAXC, int CYL, bool TWO = false, bool SPEC = false>
 __device__ __forceinline__ bool step_env_core(const EnvParams& P, const float* actions, int env, ContactLds<NB, MAXC>& L,
                                               LaneTabStore& lcs, bool live, SpecLds<CYL>* sp = nullptr)
@@ -1562,7 +1565,7 @@ __device__ __forceinline__ bool step_env_core(const EnvParams& P, const float* a
 #ifdef PMG_PROFILE
         static_assert(!TWO, "PMG_PROFILE adds workgroup barriers to wavefront 0 only: profile the one-wavefront kernels");
 #endif
-        if (((int)threadIdx.x >> 6) == 1) {                 /* the helper wavefront */
+        if (((int)threadIdx.x >> 6) == helper_wave_index<NB, SPEC>()) {   /* the helper wavefront */
             helper_wave_loop<NB, MAXC, CYL, SPEC>(P, L, lcs, sp);
             return true;
         }
